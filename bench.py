@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the EVOKE hot path on MI355X (contract: see the task statement / DESIGN.md "Measurement").
 
-    python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                            (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = one full training step of FineTune on one synthetic batch per rank: forward + backward + gradient
 all-reduce + clip_grad_value_(0.1) + two-group RAdam (the reference's FTrainer._train_epoch body,
@@ -10,9 +11,17 @@ modules/trainer_v0401.py:426-435).  Workload at N=1 = BASELINE.json configs[2] p
 not shipped), random-init weights, inputs resident in HBM before the timed region.  Weak scaling: every rank processes
 its own 32 studies; value = all ranks' studies / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the metric plus `roofline` (GEMM / implicit-GEMM kernel family, HIP-event timed
-inside the library over the timed region) and `cpu_baseline` (the CPU oracle = restatement of the reference, timed on
-this box's host cores on a bounded sample of the same workload).
+--workload decode times K whole batches of beam-search generation after W warm-up batches instead.
+
+Prints ONE JSON line on rank 0 with the metric.  A plain run sets up, warms up, times the K steps and prints that line;
+with --full it also reports `roofline` (GEMM / implicit-GEMM kernel family, HIP-event timed inside the library over one
+extra step), the host cost of issuing one step, the `decode` sub-record (beam-search generation on the trained model)
+and `cpu_baseline` (the CPU oracle = restatement of the reference, timed on this box's host cores on a bounded sample of
+the same workload).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64): the training
+workloads write the step's loss and a fixed, seeded sample of the updated parameters, the decode workload the token ids
+of the last batch.  The inputs and the initial weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -30,6 +39,7 @@ V = 1444
 # algorithmic forward+backward FLOPs per study counted on the reference (SURVEY.md section 8d / BASELINE.md section 2)
 ALG_GFLOP_PER_STUDY = {('finetune', 384): 453.2, ('finetune', 224): 60.3 * 2.868, ('pretrain', 384): 394.2, ('pretrain', 224): 141.4}
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md, chip-level parameters (dense; 5 PF is 2:1 sparse)
+DUMP_PARAM_SAMPLE = 1 << 22               # parameter values in --dump-outputs' params_sample.npy (16 MiB of float32)
 
 
 def make_args(task):
@@ -113,11 +123,29 @@ def cpu_baseline(model, kind, res, L, Li, seconds_budget=25.0):
                        'median of %d steps after 1 warm-up' % (kind, B, res, res, max(1, len(times) - 1)))
 
 
-def decode_record(model, a, rank, world, dev, with_cpu):
+def param_sample(model, n, seed=0):
+    """A fixed, seeded sample of n parameter values (with replacement) over all parameters of `model` in named_parameters()
+    order, flattened end to end, as float32 on the host."""
+    ps = [p.detach().reshape(-1) for _, p in model.named_parameters()]
+    offs = np.cumsum([0] + [p.numel() for p in ps])
+    idx = np.sort(np.random.RandomState(seed).randint(0, int(offs[-1]), size=n))
+    cut = np.searchsorted(idx, offs)
+    vals = [p[torch.from_numpy(idx[cut[i]:cut[i + 1]] - offs[i]).to(p.device)].float().cpu() for i, p in enumerate(ps)]
+    return torch.cat(vals).numpy()
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        np.save(os.path.join(path, name + '.npy'), x.astype(np.float64 if x.dtype == np.float64 else np.float32))
+
+
+def decode_record(model, a, rank, world, dev, with_cpu, n, n_warm, outputs=None):
     """BASELINE.json configs[4]: EVOKE-384 inference, beam search (default beam 4), bs 64 studies x 2 views, max_seq_len 100,
     replicas only.  One step = the whole FineTune.forward(mode='inference') of one batch (visual extractor + fusion + beam search);
     every hypothesis is extended for all max_seq_len steps as in the reference (finished beams keep running with -1000), so
-    tokens = batch x max_seq_len per step.  Returns the record dict (rank 0) or None.
+    tokens = batch x max_seq_len per step.  n batches are timed after n_warm warm-up batches.  Returns the record dict (rank 0) or None.
     roofline: the per-token decode step (one replay of the captured step: 52 kernels) against HBM -- achieved = ALGORITHMIC bytes of one
     step (the decoder-step weights once + per hypothesis the self-attention cache up to t, the cross-attention
     K/V of the 144 patches and the 1536-wide memory row, in 16-bit) / measured step time (HIP events around the replays)."""
@@ -135,12 +163,11 @@ def decode_record(model, a, rank, world, dev, with_cpu):
     # Replicas: no rank waits for another inside the measurement.  A rank that fails reports an infinite time, and the ONE collective
     # (max over ranks) sits outside the guarded region so that every rank reaches it whatever happened -- a barrier inside would hang
     # the whole job on a single rank's exception.
-    n = max(2, min(a.steps, 16))          # batches in the timed region (the pipeline fills during the first and drains during the last)
     step_ms, dt, err = [], float('inf'), None
     pipelined = os.environ.get('EVK_DECODE_PIPELINE', '1') != '0'
     depth = max(1, int(os.environ.get('EVK_DECODE_DEPTH', '4'))) if pipelined else 1
     try:
-        for _ in range(max(1, min(a.warmup, 2))):
+        for _ in range(n_warm):
             step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -166,6 +193,8 @@ def decode_record(model, a, rank, world, dev, with_cpu):
         raise err
     if rank != 0:
         return None
+    if outputs is not None:
+        outputs['sequences'] = seq.cpu().numpy().astype(np.float64)          # token ids of the last batch (exact in float64)
     dt = float(tt.item())
     if not (dt < float('inf')):
         raise RuntimeError('decode failed on another rank')
@@ -350,8 +379,12 @@ def bench_decode(a, rank, world, dev):
         for _ in range(40):
             model.visual_extractor(wb['images'])
     model.eval()
-    rec = decode_record(model, a, rank, world, dev, with_cpu=(world == 1 and not a.no_cpu_baseline))
+    outputs = {} if a.dump_outputs else None
+    rec = decode_record(model, a, rank, world, dev, with_cpu=(a.full and world == 1 and not a.no_cpu_baseline), n=a.steps, n_warm=a.warmup,
+                        outputs=outputs)
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(a.dump_outputs, outputs)
         rec.update(n_gpus=world, warmup=a.warmup, scaling='weak', vs_baseline=None, data='synthetic', ms_per_step=rec['ms_per_batch'])
         print(json.dumps(rec))
 
@@ -364,17 +397,24 @@ def main():
     ap.add_argument('--workload', default='finetune', choices=['finetune', 'pretrain', 'decode'])
     ap.add_argument('--beam', type=int, default=4)
     ap.add_argument('--decode-batch', type=int, default=64, help='studies per GPU of the decode workload (BASELINE config 5: 64)')
-    ap.add_argument('--no-decode', action='store_true', help='skip the decode sub-record of the default line')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: host issue cost, roofline, decode sub-record, CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy')
+    ap.add_argument('--no-decode', action='store_true', help='skip the decode sub-record of the --full line')
     ap.add_argument('--res', type=int, default=384)
     ap.add_argument('--batch', type=int, default=32, help='studies per GPU')
     ap.add_argument('--views', default='2', help="views per study: an integer, or 'u4' = 1..4 per study (uniform, seed 7 + rank): config 4")
     ap.add_argument('--config', type=int, default=0, help='4: BASELINE config 4 = --workload pretrain --res 384 --batch 16 --views u4')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--dump-launches', default='', help='write one CSV row per profiled launch (GEMM shapes + ms) to this path')
-    ap.add_argument('--no-prof', action='store_true', help='disable the in-library HIP-event timing of kernel families')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baseline of the --full line')
+    ap.add_argument('--dump-launches', default='', help='write one CSV row per profiled launch (GEMM shapes + ms) to this path (needs --full)')
+    ap.add_argument('--no-prof', action='store_true', help='disable the in-library HIP-event timing of kernel families (--full)')
     ap.add_argument('--no-side-streams', action='store_true', help='issue the whole step on one stream (experiment)')
     ap.add_argument('--graph', type=int, default=-1, help='1: capture the whole training step in a HIP graph, 0: eager launches, -1: default')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.dump_launches and not (a.full and not a.no_prof):
+        ap.error('--dump-launches writes the launches of the roofline step: it needs --full (and no --no-prof)')
     if a.config == 4:
         a.workload, a.res, a.batch, a.views = 'pretrain', 384, 16, 'u4'
     a.views = a.views if a.views == 'u4' else int(a.views)
@@ -490,18 +530,25 @@ def main():
         comm['backend'] = torch.distributed.get_backend()
     red.timing = False
     skipped = ops.overflow_steps(dev) - skipped0
-    # host cost of ISSUING one step, measured from an idle GPU (inside the timed loop the launch queue is full whenever the GPU is
-    # the bottleneck, so the loop's host time mostly measures the GPU): two more steps, each issued after a full synchronisation
-    issue = []
-    for _ in range(2):
+    if a.dump_outputs and rank == 0:
+        # what a caller of the step receives after the last timed step (before --full's extra steps move the weights again): the
+        # loss it returned and the parameters the optimizer left behind (a fixed, seeded sample: 348 M values do not fit 64 MB)
+        dump_outputs(a.dump_outputs, {'loss': losses[-1].detach().float().reshape(1).cpu().numpy(),
+                                      'params_sample': param_sample(model, DUMP_PARAM_SAMPLE)})
+    host_issue_ms = None
+    if a.full:
+        # host cost of ISSUING one step, measured from an idle GPU (inside the timed loop the launch queue is full whenever the GPU is
+        # the bottleneck, so the loop's host time mostly measures the GPU): two more steps, each issued after a full synchronisation
+        issue = []
+        for _ in range(2):
+            barrier()
+            t1 = time.perf_counter()
+            step()
+            issue.append(time.perf_counter() - t1)
         barrier()
-        t1 = time.perf_counter()
-        step()
-        issue.append(time.perf_counter() - t1)
-    barrier()
-    host_issue_ms = 1e3 * min(issue)
+        host_issue_ms = 1e3 * min(issue)
     fam, launched_flops = ({}, 0.0)
-    if not a.no_prof:
+    if a.full and not a.no_prof:
         # Per-kernel durations for the roofline: ONE more step of the same workload right after the timed region, with a
         # HIP-event pair around every launch (on the launch's own stream) and the side streams folded into the main one --
         # concurrent kernels share the CUs, which would inflate every event-timed duration, and the ~6k event records
@@ -532,10 +579,12 @@ def main():
     # BASELINE.json's metric is two numbers: the train-step studies/s above and decode tokens/s (config 5) -- measured on the same
     # model object right after the timed training region (every rank: replicas)
     dec_rec = None
-    if kind == 'finetune' and not a.no_decode:
+    if a.full and kind == 'finetune' and not a.no_decode:
         torch.cuda.set_stream(torch.cuda.default_stream(dev))
         try:
-            dec_rec = decode_record(model, a, rank, world, dev, with_cpu=(world == 1 and not a.no_cpu_baseline))
+            # 2-16 batches after 1-2 warm-up batches (the pipeline fills during the first timed batch and drains during the last)
+            dec_rec = decode_record(model, a, rank, world, dev, with_cpu=(world == 1 and not a.no_cpu_baseline),
+                                    n=max(2, min(a.steps, 16)), n_warm=max(1, min(a.warmup, 2)))
         except Exception as e:          # noqa: BLE001 -- the training measurement must still be reported
             dec_rec = {'metric': 'decode tokens/sec', 'value': None, 'error': repr(e)}
         model.train()
@@ -581,9 +630,9 @@ def main():
                            'launches_per_step': n / psteps, 'event_timed': '1 extra step after the timed region, single stream', 'avg_launch_us': 1e3 * ms / max(n, 1),
                            'gemm_ms_per_step': ms / psteps, 'launched_tflops': launched_flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0,
                            'family_ms_per_step': {k: v[0] / psteps for k, v in fam.items()}}
-    if kind == 'finetune' and not a.no_decode and dec_rec is not None:
+    if dec_rec is not None:
         out['decode'] = dec_rec
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         try:
             out['cpu_baseline'] = cpu_baseline(model, kind, a.res, L, Li)
         except Exception as e:          # the GPU measurement must still be reported

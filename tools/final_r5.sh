@@ -5,8 +5,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-r5final}
 mkdir -p $O
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/default.json 2> $O/default.err
-python3 bench.py --steps 20 --warmup 5 --graph 0 --no-decode --no-cpu-baseline > $O/default_eager.json 2> $O/default_eager.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/default.json 2> $O/default.err
+python3 bench.py --full --steps 20 --warmup 5 --graph 0 --no-decode --no-cpu-baseline > $O/default_eager.json 2> $O/default_eager.err
 bash tools/bench_configs_r5.sh ${1:-r5final}/cfg > $O/cfg.log 2>&1
 bash tools/forced_dist_bench.sh ${1:-r5final}/fd > $O/fd.log 2>&1
 python3 - <<PY

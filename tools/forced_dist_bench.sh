@@ -5,11 +5,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-r5fd}
 mkdir -p $O
 cd $R
-python3 bench.py --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/default.json 2> $O/default.err && \
-EVK_FORCE_DIST=1 python3 bench.py --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_allreduce.json 2> $O/forced_allreduce.err && \
-EVK_FORCE_DIST=1 EVK_GRAD_SYNC=direct python3 bench.py --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_direct.json 2> $O/forced_direct.err && \
-EVK_FORCE_DIST=1 EVK_GRAD_SYNC=16bit python3 bench.py --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_16bit.json 2> $O/forced_16bit.err && \
-EVK_FORCE_DIST=1 python3 bench.py --workload pretrain --res 224 --steps 20 --warmup 5 --no-cpu-baseline > $O/forced_pt224.json 2> $O/forced_pt224.err
+python3 bench.py --full --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/default.json 2> $O/default.err && \
+EVK_FORCE_DIST=1 python3 bench.py --full --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_allreduce.json 2> $O/forced_allreduce.err && \
+EVK_FORCE_DIST=1 EVK_GRAD_SYNC=direct python3 bench.py --full --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_direct.json 2> $O/forced_direct.err && \
+EVK_FORCE_DIST=1 EVK_GRAD_SYNC=16bit python3 bench.py --full --steps 20 --warmup 5 --no-decode --no-cpu-baseline > $O/forced_16bit.json 2> $O/forced_16bit.err && \
+EVK_FORCE_DIST=1 python3 bench.py --full --workload pretrain --res 224 --steps 20 --warmup 5 --no-cpu-baseline > $O/forced_pt224.json 2> $O/forced_pt224.err
 echo rc=$?
 python3 - <<PY
 import json,glob

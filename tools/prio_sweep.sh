@@ -6,7 +6,7 @@ O=$R/gpurun_out/${1:-r5prio}
 RES=${2:-384}
 mkdir -p $O
 cd $R
-B="--res $RES --steps 14 --warmup 4 --no-cpu-baseline --no-decode --no-prof"
+B="--full --res $RES --steps 14 --warmup 4 --no-cpu-baseline --no-decode --no-prof"
 python3 bench.py $B --graph 0 > $O/eager_main1_rm0.json 2> $O/e1.err
 EVK_RM_STREAM_PRIO=-1 python3 bench.py $B --graph 0 > $O/eager_main1_rm1.json 2> $O/e2.err
 EVK_RM_STREAM_PRIO=-1 EVK_MAIN_PRIO=0 python3 bench.py $B --graph 0 > $O/eager_main0_rm1.json 2> $O/e3.err

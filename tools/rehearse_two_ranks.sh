@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-r5two}
 mkdir -p $O
 cd $R
-EVK_DIST_BACKEND=gloo timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 6 --warmup 3 > $O/ft384_two_ranks.json 2> $O/ft384.err
+EVK_DIST_BACKEND=gloo timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 6 --warmup 3 > $O/ft384_two_ranks.json 2> $O/ft384.err
 echo rc=$?
-EVK_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --steps 6 --warmup 3 --config 4 > $O/cfg4_two_ranks.json 2> $O/cfg4.err
+EVK_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --full --gpus 2 --steps 6 --warmup 3 --config 4 > $O/cfg4_two_ranks.json 2> $O/cfg4.err
 echo rc=$?
 python3 - <<PY
 import json

@@ -10,13 +10,13 @@ mkdir -p $O
 cd $R
 run() {   # name, env...
   name=$1; shift
-  env "$@" python3 bench.py --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -5 $O/$name.err; }
+  env "$@" python3 bench.py --full --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -5 $O/$name.err; }
 }
-python3 bench.py --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 0 > $O/eager.json 2> $O/eager.err
+python3 bench.py --full --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 0 > $O/eager.json 2> $O/eager.err
 G="--graph 1"
 for v in "streams:EVK_X=1" "cover:EVK_REPLAY_LANES=cover" "streams_eqprio:EVK_MAIN_PRIO=0"; do
   name=${v%%:*}; envs=${v#*:}
-  env $envs python3 bench.py --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -5 $O/$name.err; }
+  env $envs python3 bench.py --full --workload $WL --res $RES --steps 12 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -5 $O/$name.err; }
 done
 python3 - <<PY
 import json,glob,os

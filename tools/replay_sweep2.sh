@@ -7,9 +7,9 @@ mkdir -p $O
 cd $R
 for cfg in "ft224:--res 224" "pt224:--workload pretrain --res 224" "cfg4:--config 4" "pt384:--workload pretrain --res 384"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  python3 bench.py $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 0 > $O/${name}_eager.json 2> $O/${name}_eager.err || tail -5 $O/${name}_eager.err
-  python3 bench.py $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/${name}_replay.json 2> $O/${name}_replay.err || tail -5 $O/${name}_replay.err
-  EVK_MAIN_PRIO=0 python3 bench.py $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/${name}_replay_eqprio.json 2> $O/${name}_replay_eqprio.err || tail -5 $O/${name}_replay_eqprio.err
+  python3 bench.py --full $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 0 > $O/${name}_eager.json 2> $O/${name}_eager.err || tail -5 $O/${name}_eager.err
+  python3 bench.py --full $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/${name}_replay.json 2> $O/${name}_replay.err || tail -5 $O/${name}_replay.err
+  EVK_MAIN_PRIO=0 python3 bench.py --full $args --steps 16 --warmup 4 --no-cpu-baseline --no-decode --no-prof --graph 1 > $O/${name}_replay_eqprio.json 2> $O/${name}_replay_eqprio.err || tail -5 $O/${name}_replay_eqprio.err
 done
 python3 - <<PY
 import json,glob,os

@@ -1,5 +1,5 @@
-"""profiles/*_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --steps 1 --warmup 1 --no-prof
---no-cpu-baseline`: usage traffic_json.py fetch.csv write.csv steps > out.json  (FETCH doubled on gfx950, KB -> bytes).
+"""profiles/*_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --full --steps 1 --warmup 1
+--no-prof --no-cpu-baseline`: usage traffic_json.py fetch.csv write.csv steps > out.json  (FETCH doubled on gfx950, KB -> bytes).
 The file is stamped with evoke_amd.build.source_fingerprint(): bench.py reports it as `roofline.traffic` only while it matches."""
 import json
 import os
@@ -18,7 +18,7 @@ fam = lambda n: n.startswith(FAMILY)
 names = sorted(set(fe) | set(wr), key=lambda n: -(fe.get(n, 0) + wr.get(n, 0)))
 out = {
     'fingerprint': source_fingerprint(), 'workload': ['finetune', 384, 32, 2], 'store': os.environ.get('EVK_STORE', 'f16').lower(),
-    'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only), python bench.py --steps 1 --warmup 1 '
+    'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only), python bench.py --full --steps 1 --warmup 1 '
               '--no-prof --no-cpu-baseline (finetune 384^2, 32 studies); FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies '
               '128-B requests at 64 B); KB -> bytes x1024; divided by the %g steps of the run (includes one-off initialisation)' % steps,
     'gemm_family': list(FAMILY),
