@@ -1,4 +1,4 @@
-"""Beam-search report generation on the HIP engine.
+"""Report generation on the HIP engine: beam search, and the sampling route (greedy / top-k / top-p) further down.
 
 Semantics = AttModel._sample_beam (modules/att_model.py:98-137) + CaptionModel.beam_search / beam_step
 (modules/caption_model.py:26-202, group_size = 1) + EncoderDecoder.core (modules/encoder_decoder.py:396-404).
@@ -467,31 +467,26 @@ class _DecoderState:
         return ops.log_softmax(logits.view(logits.shape[0], -1), self.dec.vocab_size + 1)
 
 
-class _BeamSession:
-    """Everything a beam search over B samples x `beam` hypotheses x max_len positions owns on the device -- self-attention caches, cache
-    row tables, cross-attention K / V, relational memory, beam bookkeeping arrays, the log-probability buffer -- allocated ONCE and kept
+class _Session:
+    """What a decode session over B samples x R rows x max_len positions owns on the device whatever the search -- self-attention caches,
+    cache row table, cross-attention K / V, relational memory, the log-probability buffer, the position counter -- allocated ONCE and kept
     on the decoder, together with the captured per-token launch sequence and its replay plan.  A generate call then only refills the
     buffers (cross K / V of the new batch, the first position's state) and replays: no allocation, no capture, no plan build per batch
-    (13 ms of host time per 64-study batch otherwise, during which the decode stream sits idle)."""
+    (13 ms of host time per 64-study batch otherwise, during which the decode stream sits idle).  A subclass supplies _body() (the
+    launches of one token step) and _run_iter() (what happens around the token loop)."""
 
-    def __init__(self, dec, B, beam, max_len, S, dev, slot=0):
+    def __init__(self, dec, B, R, max_len, S, dev, slot=0):
         model = dec.model
         self.slot = slot
         d, nl = model.d_model, len(model.decoder.layers)
-        R = B * beam
-        self.dec, self.B, self.beam, self.max_len, self.R = dec, B, beam, max_len, R
+        self.dec, self.B, self.max_len, self.R = dec, B, max_len, R
         self.kc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
         self.vc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
         self.st = None                    # R-row decoder state, built on first use (needs an encoder output for its geometry)
-        self.beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
-        self.beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
-        self.best_p = torch.empty(B, dtype=F32, device=dev)
-        self.best_seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
         self.words = torch.empty(R, dtype=torch.long, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pos = torch.ones(1, dtype=torch.long, device=dev)
         self.logp_buf = torch.empty(R, dec.vocab_size + 1, dtype=F32, device=dev)
-        self.base = torch.arange(B, device=dev).unsqueeze(1)
         self.graph = self.plan = None
         self.fused_key = None
         # the encoder key mask of the CURRENT batch, in a buffer the session owns: the captured per-token step records a pointer, so a
@@ -506,35 +501,19 @@ class _BeamSession:
             except Exception:          # noqa: BLE001 -- interpreter shutdown
                 pass
 
-    def _book_kernel(self, last):
-        """one launch (csrc/beam.hip): top-beam, sequence / cache-row-table / relational-memory reorder in place, finished-beam tracking,
-        -1000 penalty, next input tokens -- and, between steps, the position counter's increment and the row table's next column"""
-        dec, st, lp = self.dec, self.st, self.logp_buf
-        H.check(H.lib.evk_beam_step(H.ptr(lp), lp.shape[-1], dec.vocab_size + 1, self.beam, self.B, self.max_len, H.ptr(self.pos), dec.eos_idx,
-                                    int(last), H.ptr(self.beam_sum), H.ptr(self.beam_seq), H.ptr(self.best_p), H.ptr(self.best_seq),
-                                    H.ptr(self.words), H.ptr(st.mem32 if st.mem32 is not None else st.mem),
-                                    st.mem[0].numel() * (2 if st.mem32 is not None else 1), H.ptr(st.anc), st.anc.shape[1],
-                                    None if last else H.ptr(self.pos), H.ptr(self.ticket), H.ptr(st.tmem) if st.mem32 is None else None,
-                                    H.stream()), 'beam_step')
-
-    def _body(self):
-        """positions 1 .. max_len-2: bookkeeping at position `pos` (which also advances it), then the decoder step that writes pos + 1"""
-        self._book_kernel(False)
-        self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
-
-    def run(self, enc, src_mask, return_scores=False, step_hook=None):
-        it = self.run_iter(enc, src_mask, return_scores, step_hook)
+    def run(self, *args, **kw):
+        it = self.run_iter(*args, **kw)
         try:
             while True:
                 next(it)
         except StopIteration as e:
             return e.value
 
-    def run_iter(self, enc, src_mask, return_scores=False, step_hook=None, burst=0):
+    def run_iter(self, *args, **kw):
         """_run_iter under eval mode and no_grad for as long as the generator RUNS (a generator's body executes at next(), long after
-        beam_search's own eval / no_grad scope has been left; no_grad is per THREAD: the scope is opened around every next(), whichever
+        the caller's own eval / no_grad scope has been left; no_grad is per THREAD: the scope is opened around every next(), whichever
         thread calls it)"""
-        it = self._run_iter(enc, src_mask, return_scores, step_hook, burst)
+        it = self._run_iter(*args, **kw)
         dec = self.dec
         while True:
             # (nn.Module.eval / train walk the whole module tree: only when the decoder really is in training mode -- the serving loop
@@ -552,6 +531,147 @@ class _BeamSession:
                     dec.train(True)
             yield v
 
+    def _refill(self, enc, src_mask):
+        """the new batch into the session's buffers (the captured step reads them there); (re)builds the R-row state when the decoder's
+        derived weights changed -> the session's copy of the encoder key mask (or None)"""
+        dec, B, dev = self.dec, self.B, enc.device
+        model = dec.model
+        # cross-attention K / V of this batch
+        for i, layer in enumerate(model.decoder.layers):
+            ops.copy_kernel(self.kc[i], layer.src_attn.linears[1](enc))
+            ops.copy_kernel(self.vc[i], layer.src_attn.linears[2](enc))
+        if src_mask is not None:
+            if self.src_mask is None:
+                self.src_mask = torch.empty(B, src_mask.shape[-1], dtype=torch.uint8, device=dev)
+            if tuple(src_mask.shape) != tuple(self.src_mask.shape) or src_mask.dtype != torch.uint8:
+                raise ValueError('decode session: encoder mask %s %s does not fit the session (%s uint8)'
+                                 % (tuple(src_mask.shape), src_mask.dtype, tuple(self.src_mask.shape)))
+            self.src_mask.copy_(src_mask)                 # (B x S bytes, not a multiple of 4 in general: torch's copy, outside the capture)
+            src_mask = self.src_mask
+        elif self.src_mask is not None:
+            raise ValueError('decode session built for masked encoder states got an unmasked batch')
+        fused = _fused_weights(model)
+        if self.st is None or self.fused_key is not fused:
+            # (re)build the R-row state around the session's buffers; derived weights changed -> the captured step is stale as well
+            self.st = _DecoderState(dec, enc, src_mask, self.max_len, cross_kv=(self.kc, self.vc), rows=self.R)
+            self.fused_key = fused
+            if self.plan is not None:
+                _PLANS.append((self.plan, self.graph, torch.cuda.Event()))
+                _PLANS[-1][2].record()
+            self.graph = self.plan = None
+        self.st.enc, self.st.src_mask = enc, src_mask
+        return src_mask
+
+    def _drive(self, n_body, first, step_hook, burst, extra=()):
+        """the token loop: n_body times _body(), body number i writing the log-probabilities of position i + first (step_hook(position,
+        logp_buf, *extra) is called right after it).  On first use two bodies run as warm-up, the third is captured and turned into a
+        replay plan; the loop then replays.  A generator: yields after every issued step (see _run_iter of the subclasses)."""
+        dev = self.logp_buf.device
+        done = 0
+        cur = torch.cuda.current_stream()
+        if self.graph is None and n_body > 3 and _GRAPH_ENABLED[0]:
+            hook = step_hook if step_hook is not None else (lambda *a: None)
+            side = _capture_stream(dev, ('warm', self.slot))
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):                           # warm-up iterations (real steps) off the launching stream
+                self._body()
+                hook(first, self.logp_buf, *extra)
+                self._body()
+                hook(first + 1, self.logp_buf, *extra)
+            cur.wait_stream(side)
+            done = 2
+            try:
+                # captured by hand (capture_begin / capture_end on a side stream), not through torch.cuda.graph(): the context manager
+                # opens with a DEVICE-WIDE synchronize, which would make this decode wait for the next batch's encoders
+                graph = torch.cuda.CUDAGraph(keep_graph=_REPLAYER[0])
+                cap = _capture_stream(dev, ('capture', self.slot))
+                cap.wait_stream(cur)
+                with torch.cuda.stream(cap):
+                    # (a pool of the session's own: searches in flight at the same time replay concurrently, and a handle must not
+                    # outlive the last graph that used it)
+                    self.pool = torch.cuda.graph_pool_handle()
+                    # (thread_local: the worker threads of generate_pipelined download results / record events on OTHER streams meanwhile)
+                    graph.capture_begin(pool=self.pool, capture_error_mode='thread_local')
+                    try:
+                        self._body()
+                    finally:
+                        graph.capture_end()
+                cur.wait_stream(cap)
+                self.graph = graph
+            except Exception as e:                                   # stay on the HIP path, just without the graph
+                import warnings
+                warnings.warn('decode: HIP graph capture failed (%s); running the steps eagerly' % e)
+                self.graph = None
+            if self.graph is not None and _REPLAYER[0]:
+                # the library's own replayer (csrc/replay.hip): plain launches, ~3 us of host time per node (hipGraphLaunch: 7-12 us)
+                plan = H.lib.evk_replay_build(C.c_void_p(self.graph.raw_cuda_graph()), 16)
+                if not plan:
+                    import warnings
+                    warnings.warn('decode: replay plan refused (%s); using hipGraphLaunch' % H.lib.evk_last_error().decode())
+                    if hasattr(self.graph, 'instantiate'):
+                        self.graph.instantiate()
+                self.plan = plan or None
+                if self.plan is not None:
+                    info = (C.c_int64 * 7)()
+                    H.check(H.lib.evk_replay_info(self.plan, info), 'replay_info')
+                    self.step_launches = int(info[1])                 # kernel nodes of ONE captured token step
+        stats['step_launches'] = getattr(self, 'step_launches', None)
+        bursts = burst > 0 and self.plan is not None and step_hook is None
+        if bursts:
+            yield -1
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        it_ = done
+        while bursts and it_ < n_body:
+            n = min(int(burst), n_body - it_)
+            H.check(H.lib.evk_replay_run_n(self.plan, H.stream(), n), 'replay_run_n')
+            it_ += n
+            yield it_ - 1
+        for it_ in range(it_, n_body):
+            if self.plan is not None:
+                H.check(H.lib.evk_replay_run(self.plan, H.stream()), 'replay_run')
+            elif self.graph is not None:
+                self.graph.replay()
+            else:
+                self._body()
+            if step_hook is not None:
+                step_hook(it_ + first, self.logp_buf, *extra)
+            yield it_
+        ev1.record()
+        stats['step_events'] = (ev0, ev1, max(0, n_body - done))      # per-token step time = elapsed / count (bench.py)
+        stats['graph'] = self.graph is not None
+        stats['replayer'] = self.plan is not None
+        stats['fused_bookkeeping'] = True
+
+
+class _BeamSession(_Session):
+    """The session of a beam search over B samples x `beam` hypotheses: the shared state plus the beam bookkeeping arrays."""
+
+    def __init__(self, dec, B, beam, max_len, S, dev, slot=0):
+        super().__init__(dec, B, B * beam, max_len, S, dev, slot)
+        self.beam = beam
+        self.beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
+        self.beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
+        self.best_p = torch.empty(B, dtype=F32, device=dev)
+        self.best_seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
+        self.base = torch.arange(B, device=dev).unsqueeze(1)
+
+    def _book_kernel(self, last):
+        """one launch (csrc/beam.hip): top-beam, sequence / cache-row-table / relational-memory reorder in place, finished-beam tracking,
+        -1000 penalty, next input tokens -- and, between steps, the position counter's increment and the row table's next column"""
+        dec, st, lp = self.dec, self.st, self.logp_buf
+        H.check(H.lib.evk_beam_step(H.ptr(lp), lp.shape[-1], dec.vocab_size + 1, self.beam, self.B, self.max_len, H.ptr(self.pos), dec.eos_idx,
+                                    int(last), H.ptr(self.beam_sum), H.ptr(self.beam_seq), H.ptr(self.best_p), H.ptr(self.best_seq),
+                                    H.ptr(self.words), H.ptr(st.mem32 if st.mem32 is not None else st.mem),
+                                    st.mem[0].numel() * (2 if st.mem32 is not None else 1), H.ptr(st.anc), st.anc.shape[1],
+                                    None if last else H.ptr(self.pos), H.ptr(self.ticket), H.ptr(st.tmem) if st.mem32 is None else None,
+                                    H.stream()), 'beam_step')
+
+    def _body(self):
+        """positions 1 .. max_len-2: bookkeeping at position `pos` (which also advances it), then the decoder step that writes pos + 1"""
+        self._book_kernel(False)
+        self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
+
     def _run_iter(self, enc, src_mask, return_scores=False, step_hook=None, burst=0):
         """run() as a generator that yields after every issued token step: a scheduler that drives several sessions (one per HIP stream)
         round-robin keeps all their launch queues fed (FineTune.generate_pipelined) -- issuing one session's ~3k launches in one go
@@ -563,31 +683,8 @@ class _BeamSession:
         dev, V1 = enc.device, dec.vocab_size + 1
         hook = step_hook if step_hook is not None else (lambda *a: None)
         model = dec.model
-        # cross-attention K / V of this batch, into the session's buffers (the captured step reads them there)
-        for i, layer in enumerate(model.decoder.layers):
-            ops.copy_kernel(self.kc[i], layer.src_attn.linears[1](enc))
-            ops.copy_kernel(self.vc[i], layer.src_attn.linears[2](enc))
-        if src_mask is not None:
-            if self.src_mask is None:
-                self.src_mask = torch.empty(B, src_mask.shape[-1], dtype=torch.uint8, device=dev)
-            if tuple(src_mask.shape) != tuple(self.src_mask.shape) or src_mask.dtype != torch.uint8:
-                raise ValueError('beam session: encoder mask %s %s does not fit the session (%s uint8)'
-                                 % (tuple(src_mask.shape), src_mask.dtype, tuple(self.src_mask.shape)))
-            self.src_mask.copy_(src_mask)                 # (B x S bytes, not a multiple of 4 in general: torch's copy, outside the capture)
-            src_mask = self.src_mask
-        elif self.src_mask is not None:
-            raise ValueError('beam session built for masked encoder states got an unmasked batch')
-        fused = _fused_weights(model)
-        if self.st is None or self.fused_key is not fused:
-            # (re)build the R-row state around the session's buffers; derived weights changed -> the captured step is stale as well
-            self.st = _DecoderState(dec, enc, src_mask, max_len, cross_kv=(self.kc, self.vc), rows=R)
-            self.fused_key = fused
-            if self.plan is not None:
-                _PLANS.append((self.plan, self.graph, torch.cuda.Event()))
-                _PLANS[-1][2].record()
-            self.graph = self.plan = None
+        src_mask = self._refill(enc, src_mask)
         st = self.st
-        st.enc, st.src_mask = enc, src_mask
         # ---- position 0: B rows, eagerly (modules/att_model.py:118-124: one decoder call with [BOS], then the features are tiled x beam)
         st0 = _DecoderState(dec, enc, src_mask, 1, cross_kv=(self.kc, self.vc))
         logp0 = st0.step(torch.full((B,), dec.bos_idx, dtype=torch.long, device=dev))            # (B, V+1)
@@ -631,87 +728,85 @@ class _BeamSession:
             if st.anc is None:
                 raise RuntimeError('beam session needs the cache row table (head dim 64, max_seq_len <= 256)')
             hook(1, self.logp_buf, self.beam_sum)
-            n_body = max_len - 2
-            done = 0
-            cur = torch.cuda.current_stream()
-            if self.graph is None and n_body > 3 and _GRAPH_ENABLED[0]:
-                side = _capture_stream(dev, ('warm', self.slot))
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):                           # warm-up iterations (real steps) off the launching stream
-                    self._body()
-                    hook(2, self.logp_buf, self.beam_sum)
-                    self._body()
-                    hook(3, self.logp_buf, self.beam_sum)
-                cur.wait_stream(side)
-                done = 2
-                try:
-                    # captured by hand (capture_begin / capture_end on a side stream), not through torch.cuda.graph(): the context manager
-                    # opens with a DEVICE-WIDE synchronize, which would make this decode wait for the next batch's encoders
-                    graph = torch.cuda.CUDAGraph(keep_graph=_REPLAYER[0])
-                    cap = _capture_stream(dev, ('capture', self.slot))
-                    cap.wait_stream(cur)
-                    with torch.cuda.stream(cap):
-                        # (a pool of the session's own: searches in flight at the same time replay concurrently, and a handle must not
-                        # outlive the last graph that used it)
-                        self.pool = torch.cuda.graph_pool_handle()
-                        # (thread_local: the worker threads of generate_pipelined download results / record events on OTHER streams meanwhile)
-                        graph.capture_begin(pool=self.pool, capture_error_mode='thread_local')
-                        try:
-                            self._body()
-                        finally:
-                            graph.capture_end()
-                    cur.wait_stream(cap)
-                    self.graph = graph
-                except Exception as e:                                   # stay on the HIP path, just without the graph
-                    import warnings
-                    warnings.warn('decode: HIP graph capture failed (%s); running the steps eagerly' % e)
-                    self.graph = None
-                if self.graph is not None and _REPLAYER[0]:
-                    # the library's own replayer (csrc/replay.hip): plain launches, ~3 us of host time per node (hipGraphLaunch: 7-12 us)
-                    plan = H.lib.evk_replay_build(C.c_void_p(self.graph.raw_cuda_graph()), 16)
-                    if not plan:
-                        import warnings
-                        warnings.warn('decode: replay plan refused (%s); using hipGraphLaunch' % H.lib.evk_last_error().decode())
-                        if hasattr(self.graph, 'instantiate'):
-                            self.graph.instantiate()
-                    self.plan = plan or None
-                    if self.plan is not None:
-                        info = (C.c_int64 * 7)()
-                        H.check(H.lib.evk_replay_info(self.plan, info), 'replay_info')
-                        self.step_launches = int(info[1])                 # kernel nodes of ONE captured token step
-            stats['step_launches'] = getattr(self, 'step_launches', None)
-            bursts = burst > 0 and self.plan is not None and step_hook is None
-            if bursts:
-                yield -1
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-            it_ = done
-            while bursts and it_ < n_body:
-                n = min(int(burst), n_body - it_)
-                H.check(H.lib.evk_replay_run_n(self.plan, H.stream(), n), 'replay_run_n')
-                it_ += n
-                yield it_ - 1
-            for it_ in range(it_, n_body):
-                if self.plan is not None:
-                    H.check(H.lib.evk_replay_run(self.plan, H.stream()), 'replay_run')
-                elif self.graph is not None:
-                    self.graph.replay()
-                else:
-                    self._body()
-                if step_hook is not None:
-                    step_hook(it_ + 2, self.logp_buf, self.beam_sum)       # body number it_ wrote the log-probabilities of position it_ + 2
-                yield it_
-            ev1.record()
-            stats['step_events'] = (ev0, ev1, max(0, n_body - done))      # per-token step time = elapsed / count (bench.py)
-            stats['graph'] = self.graph is not None
-            stats['replayer'] = self.plan is not None
-            stats['fused_bookkeeping'] = True
+            # positions 1 .. max_len-2: body number i writes the log-probabilities of position i + 2
+            yield from self._drive(max_len - 2, 2, step_hook, burst, (self.beam_sum,))
             self._book_kernel(True)                                      # t = max_len - 1: every live beam is closed
             _reap_plans()
         seq = self.best_seq.clone()
         if return_scores:
             return seq, self.best_p.clone()
         return seq
+
+
+class _SampleSession(_Session):
+    """The session of AttModel._sample over B samples x sample_n rows: the shared state with the identity row table (rows never trade
+    places, so neither the caches nor the memory are permuted) plus the arrays of csrc/sample.hip.  The options are kernel arguments of the
+    captured step, so they are part of the session's key (see sample())."""
+
+    def __init__(self, dec, B, n, max_len, S, dev, opts, return_logprobs, slot=0):
+        super().__init__(dec, B, B * n, max_len, S, dev, slot)
+        R, V1 = self.R, dec.vocab_size + 1
+        self.opts = opts
+        self.seq = torch.empty(R, max_len, dtype=torch.long, device=dev)
+        self.unfinished = torch.empty(R, dtype=torch.uint8, device=dev)
+        self.seq_logprobs = torch.empty(R, max_len, V1, dtype=F32, device=dev) if return_logprobs else None
+        self.uniforms = torch.empty(R, max_len, dtype=F32, device=dev) if opts['method'] != 0 else None
+        self.mem0 = None                  # the relational memory every row starts from
+
+    def _book_kernel(self, last):
+        """one launch (csrc/sample.hip): constraint, trigram penalty, stored row, choice, finished rows, next input tokens -- and, between
+        steps, the position counter's increment"""
+        _sample_step(self.dec, self.logp_buf, self.pos, self.seq, self.unfinished, self.words, self.seq_logprobs, self.uniforms, self.opts,
+                     self.B, None if last else self.pos, self.ticket)
+
+    def _body(self):
+        """the choice at position `pos` (which also advances it), then the decoder step that reads the chosen words at pos + 1"""
+        self._book_kernel(False)
+        self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
+
+    def _run_iter(self, enc, src_mask, uniforms=None, step_hook=None, burst=0):
+        """as _BeamSession._run_iter (same yields, same burst protocol) -> (seq, seq_logprobs or None)"""
+        dec, max_len = self.dec, self.max_len
+        hook = step_hook if step_hook is not None else (lambda *a: None)
+        self._refill(enc, src_mask)
+        st = self.st
+        # ---- every row starts from the initial memory and [BOS] at position 0 (att_model.py:157-173)
+        if self.mem0 is None or self.mem0.shape != st.mem.shape:
+            self.mem0 = dec.model.rm.init_memory(self.R, enc.device).to(st.mem.dtype).contiguous()
+            self.mem0_32 = self.mem0.float().contiguous()
+        st.mem.copy_(self.mem0)
+        if st.mem32 is not None:
+            st.mem32.copy_(self.mem0_32)
+        elif _RM_STEP[0]:
+            if st.tmem is None:
+                st.tmem = torch.empty_like(st.mem)
+            H.check(H.lib.evk_act_fwd(H.ptr(st.mem), H.ptr(st.tmem), st.mem.numel(), H.ACT_TANH, H.stream()), 'act_fwd')
+        self.seq.fill_(dec.pad_idx)
+        self.unfinished.fill_(1)
+        if self.seq_logprobs is not None:
+            self.seq_logprobs.zero_()
+        if self.uniforms is not None:
+            self.uniforms.copy_(uniforms)
+        self.pos.zero_()
+        self.ticket.zero_()
+        self.words.fill_(dec.bos_idx)
+        st.step_static(self.words, self.pos, None, out=self.logp_buf)        # position 0 (and builds the row table on first use: the identity)
+        if st.anc is None:
+            raise RuntimeError('sample session needs the cache row table (head dim 64, max_seq_len <= 256)')
+        hook(0, self.logp_buf)
+        # positions 0 .. max_len-2: body number i chooses the word of position i and writes the log-probabilities of position i + 1
+        yield from self._drive(max_len - 1, 1, step_hook, burst)
+        self._book_kernel(True)                                               # the last position: nothing follows it
+        _reap_plans()
+        return self.seq.clone(), (self.seq_logprobs.clone() if self.seq_logprobs is not None else None)
+
+
+def _sample_step(dec, logp, pos, seq, unfinished, words, seq_logprobs, uniforms, opts, block_rows, pos_advance, ticket):
+    H.check(H.lib.evk_sample_step(H.ptr(logp), logp.stride(0), dec.vocab_size + 1, seq.shape[0], seq.shape[1], H.ptr(pos), dec.eos_idx, dec.pad_idx,
+                                  block_rows if opts['block_trigrams'] else 0, int(opts['decoding_constraint']), C.c_float(opts['temperature']),
+                                  opts['method'], C.c_float(opts['param']), H.ptr(seq), H.ptr(unfinished), H.ptr(words),
+                                  H.ptr(seq_logprobs) if seq_logprobs is not None else None, H.ptr(uniforms) if uniforms is not None else None,
+                                  H.ptr(pos_advance), H.ptr(ticket), H.stream()), 'sample_step')
 
 
 import weakref  # noqa: E402
@@ -761,6 +856,108 @@ def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=
         return ses.run(enc, src_mask, return_scores, step_hook)
     finally:
         dec.train(was_training)
+
+
+SAMPLE_GREEDY, SAMPLE_ALL, SAMPLE_TOPK, SAMPLE_TOPP = 0, 1, 2, 3           # the method codes of evk_sample_step
+
+
+def parse_sample_method(sample_method):
+    """CaptionModel.sample_next_word's reading of `sample_method` (caption_model.py:363-398) -> (method code of evk_sample_step, parameter):
+    'greedy'; 'top<k>' with k >= 1; 'top<p>' with 0 < p < 1; every other name ('sample', and 'beam_search' once beam_size is 1) draws from
+    the unfiltered distribution, as the reference's final `else` does.  'gumbel' is not on the path."""
+    if sample_method == 'greedy':
+        return SAMPLE_GREEDY, 0.0
+    if sample_method == 'gumbel':
+        raise NotImplementedError("sample_method 'gumbel' (gumbel-softmax sampling) is not on the path")
+    if sample_method.startswith('top'):
+        top_num = float(sample_method[3:])
+        if 0 < top_num < 1:
+            return SAMPLE_TOPP, top_num
+        if int(top_num) < 1:
+            raise ValueError('sample_method %r: k must be at least 1' % sample_method)
+        return SAMPLE_TOPK, float(int(top_num))
+    return SAMPLE_ALL, 0.0
+
+
+@torch.no_grad()
+def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=None, uniforms=None, slot=0, as_iterator=False, burst=0):
+    """AttModel._sample (modules/att_model.py:139-224) -> (seq (R, max_seq_len) int64 padded with [PAD], seq_logprobs (R, max_seq_len, V+1)
+    f32 or None), R = B * sample_n rows with the sample_n copies of a study next to each other.  Options read from `args`: sample_method
+    (parse_sample_method), temperature, sample_n, decoding_constraint, block_trigrams -- the reference blocks only the first B of the R rows
+    (its loop runs over batch_size), and so does this.  Always max_seq_len steps without a host synchronisation: rows that have emitted [EOS]
+    continue as [PAD] with zero log-probability rows, which is what the reference's early exit returns.
+    uniforms: (R, max_seq_len) f32 in [0, 1), one per row and position, for the stochastic methods (default: torch.rand on the device, from
+    args['generator'] if given); step_hook(t, logp): test instrument, called on the launching stream right before the choice at position t
+    consumes `logp` (f32 (R, >= V+1), may be edited in place); slot / as_iterator / burst: as beam_search."""
+    was_training = dec.training
+    dec.eval()
+    try:
+        max_len, n = int(args['max_seq_len']), int(args.get('sample_n', 1))
+        if args.get('group_size', 1) != 1:
+            raise NotImplementedError('diverse sampling / diverse beam search (group_size > 1, AttModel._diverse_sample) is not on the path')
+        if n < 1:
+            raise ValueError('sample_n must be at least 1')
+        method, param = parse_sample_method(args.get('sample_method', 'greedy'))
+        temperature = float(args.get('temperature', 1.0))
+        if method != SAMPLE_GREEDY and not temperature > 0:
+            raise ValueError('temperature must be positive')
+        if method == SAMPLE_TOPK and param > dec.vocab_size + 1:
+            raise ValueError('top-k: k exceeds the vocabulary')
+        opts = dict(method=method, param=param, temperature=temperature, decoding_constraint=int(bool(args.get('decoding_constraint', 0))),
+                    block_trigrams=int(bool(args.get('block_trigrams', 0))))
+        enc, src_mask = dec.encode(enc_states, enc_mask)
+        B, S, dev = enc.shape[0], enc.shape[1], enc.device
+        R = B * n
+        if method != SAMPLE_GREEDY:
+            if uniforms is None:
+                uniforms = torch.rand(R, max_len, dtype=F32, device=dev, generator=args.get('generator'))
+            if tuple(uniforms.shape) != (R, max_len):
+                raise ValueError('uniforms must be (%d, %d)' % (R, max_len))
+            uniforms = uniforms.to(device=dev, dtype=F32)
+        if not _session_ok(dec, args, enc_states):
+            if as_iterator:
+                raise NotImplementedError('stepwise sampling needs the session path')
+            return _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_hook, uniforms)
+        # ('sample' in front: a beam session's key starts with an integer)
+        key = ('sample', B, n, max_len, S, dev.index, src_mask is None, slot, bool(return_logprobs), tuple(sorted(opts.items())))
+        sessions = _SESSIONS.setdefault(dec, {})
+        ses = sessions.pop(key, None)
+        if ses is None:
+            ses = _SampleSession(dec, B, n, max_len, S, dev, opts, return_logprobs, slot)
+            while len(sessions) >= 6:
+                sessions.pop(next(iter(sessions)))
+        sessions[key] = ses
+        if as_iterator:
+            return ses.run_iter(enc, src_mask, uniforms, step_hook, burst)
+        return ses.run(enc, src_mask, uniforms, step_hook)
+    finally:
+        dec.train(was_training)
+
+
+def _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_hook, uniforms):
+    """sample() without the persistent session (head dims other than 64, max_seq_len > 256, or the debugging switches): the decoder steps
+    run eagerly with the position on the host; the choice is the same kernel."""
+    B, dev, V1 = enc.shape[0], enc.device, dec.vocab_size + 1
+    R = B * n
+    cross = ([l.src_attn.linears[1](enc) for l in dec.model.decoder.layers], [l.src_attn.linears[2](enc) for l in dec.model.decoder.layers])
+    st = _DecoderState(dec, enc, src_mask, max_len, cross_kv=cross, rows=R)
+    if n > 1:
+        # (the eager step's attention wants one K / V row per query row)
+        st.kc = [k.repeat_interleave(n, 0) for k in st.kc]
+        st.vc = [v.repeat_interleave(n, 0) for v in st.vc]
+        st.src_mask = src_mask.repeat_interleave(n, 0) if src_mask is not None else None
+    seq = torch.full((R, max_len), dec.pad_idx, dtype=torch.long, device=dev)
+    unfinished = torch.ones(R, dtype=torch.uint8, device=dev)
+    words = torch.full((R,), dec.bos_idx, dtype=torch.long, device=dev)
+    seq_logprobs = torch.zeros(R, max_len, V1, dtype=F32, device=dev) if return_logprobs else None
+    pos = torch.zeros(1, dtype=torch.long, device=dev)
+    ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+    for t in range(max_len):
+        logp = st.step(words)
+        if step_hook is not None:
+            step_hook(t, logp)
+        _sample_step(dec, logp, pos, seq, unfinished, words, seq_logprobs, uniforms, opts, B, pos, ticket)
+    return seq, seq_logprobs
 
 
 @torch.no_grad()

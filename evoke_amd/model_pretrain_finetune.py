@@ -22,6 +22,17 @@ from .trunk import ResNet
 NO_FINDING = "there is no evidence of pulmonary."
 
 
+def decode_route(args):
+    """Which decode route AttModel._sample takes for these options (modules/att_model.py:150-153) -> 'beam' or 'sample': beam_size > 1 with
+    sample_method 'greedy' / 'beam_search' is the beam search; group_size > 1 would be _diverse_sample, which is not on the path; everything
+    else -- beam_size 1, or any other sample_method -- is the sampling route (decode.sample)."""
+    if args.get('beam_size', 1) > 1 and args.get('sample_method', 'greedy') in ('greedy', 'beam_search'):
+        return 'beam'
+    if args.get('group_size', 1) > 1:
+        raise NotImplementedError('diverse sampling (group_size > 1, AttModel._diverse_sample) is not on the path')
+    return 'sample'
+
+
 def _to_device_async(t, device):
     if t.is_cuda:
         return t
@@ -153,8 +164,11 @@ class FineTune(_Base):
         if mode == 'train':
             logits = self.text_decoder.forward_logits(input_ids, encoder_hidden_states, attention_mask, encoder_attention_mask, pending)
             return losses.lm_loss(logits, input_ids, attention_mask, self.text_decoder.vocab_size + 1)
-        from .decode import beam_search
-        output = beam_search(self.text_decoder, encoder_hidden_states, encoder_attention_mask, self.args)
+        from .decode import beam_search, sample
+        if decode_route(self.args) == 'beam':
+            output = beam_search(self.text_decoder, encoder_hidden_states, encoder_attention_mask, self.args)
+        else:
+            output = sample(self.text_decoder, encoder_hidden_states, encoder_attention_mask, self.args)[0]
         gen_texts = self.tokenizer.decode_batch(output.cpu().tolist())
         ops.check_forward_guard(output.device, block=True)          # (the .cpu() above has synchronised: the verdict is there)
         gt_texts = self.tokenizer.decode_batch(input_ids.cpu().tolist())
@@ -182,7 +196,11 @@ class FineTune(_Base):
         if self.decoder_kind != 'r2gen':
             yield from self._generate_encoders_ahead(batches, mode)
             return
-        from .decode import beam_search
+        from .decode import beam_search, sample
+        if decode_route(self.args) == 'beam':
+            search, result = beam_search, (lambda v: v)
+        else:
+            search, result = sample, (lambda v: v[0])            # (seq, seq_logprobs): the ids
         depth = max(1, int(depth if depth is not None else os.environ.get('EVK_DECODE_DEPTH', '4')))
         # EVK_DECODE_THREADS=0 (default since round 5): this thread issues the token steps of all searches round-robin; 1: one host thread per
         # search in flight issues its token loop (evk_replay_run_n, GIL released).  With every stream at the default priority and four searches
@@ -238,10 +256,10 @@ class FineTune(_Base):
                 x.record_stream(dec_s[slot])
                 enc_mask.record_stream(dec_s[slot])
                 try:
-                    gen = beam_search(self.text_decoder, x, enc_mask, self.args, slot=slot, as_iterator=True, burst=burst if threaded else 0)
+                    gen = search(self.text_decoder, x, enc_mask, self.args, slot=slot, as_iterator=True, burst=burst if threaded else 0)
                     job = [slot, gen, report_ids, None, None, None]
                 except NotImplementedError:              # no session path for this geometry: the whole search in one go
-                    return [slot, None, report_ids, beam_search(self.text_decoder, x, enc_mask, self.args), None, None]
+                    return [slot, None, report_ids, result(search(self.text_decoder, x, enc_mask, self.args)), None, None]
                 if threaded:
                     # everything in front of the token loop (cross-attention K / V, position 0, on first use the graph capture, which
                     # must not meet another thread's allocations) from THIS thread; the loop itself from a worker
@@ -258,7 +276,7 @@ class FineTune(_Base):
                     next(job[1])
                     return False
                 except StopIteration as e:
-                    job[3] = e.value
+                    job[3] = result(e.value)
                     job[1] = None
                     return True
 

@@ -439,6 +439,23 @@ int evk_beam_step(const float* logp, int32_t ld, int32_t V1, int32_t beam, int32
                   int32_t force_end, float* beam_sum, int64_t* beam_seq, float* best_p, int64_t* best_seq, int64_t* words, void* mem,
                   int32_t mem_row, int32_t* anc, int32_t anc_cols, int64_t* pos_advance, int32_t* ticket, void* mem2, evk_stream_t stream);
 /* mem2 (optional): a second per-hypothesis state of mem_row 16-bit values re-ordered like mem (tanh of the relational memory) */
+/* One launch for everything AttModel._sample does between two decoder steps (sample.hip; modules/att_model.py:176-221 and
+ * CaptionModel.sample_next_word, modules/caption_model.py:363-401), for R independent rows.  logp [R][ld] f32 log-probs (V1 = V+1 valid
+ * columns, V1 <= 4096); *pos = position t being written.  In the reference's order: decoding_constraint != 0 and t > 0: column seq[r][t-1]
+ * becomes -inf; t >= 3 and r < block_rows: every earlier trigram (seq[r][t-2], seq[r][t-1], w) of the row counts against w,
+ * logp[w] += (count * -0.693f) * 2.0f (att_model.py:189-208; the reference blocks the first batch_size of its sample_n-repeated rows only,
+ * hence block_rows); seq_logprobs [R][max_len][V1] (or NULL) receives the row as it stands now, zeros for a row that had finished.
+ * method 0 = greedy arg-max (ties -> lowest index); 1 = categorical draw from softmax(logp / temperature); 2 = the same among the
+ * param = k largest entries; 3 = among the nucleus of probability param = p (descending order, an entry is kept while the cumulative
+ * probability before it is < p).  The draw is an inverse CDF over the kept entries in column order with u = uniforms[r][t] (f32
+ * [R][max_len] in [0, 1), required for methods 1-3): the first column whose running weight exceeds u * total.  Bookkeeping
+ * (att_model.py:213-221): unfinished [R] (uint8, in / out) is set at t = 0 to (word != eos); later a finished row emits `pad` and
+ * unfinished &= (word != eos); seq [R][max_len] (int64) gets the word at column t, words [R] the next decoder input.
+ * pos_advance / ticket as in evk_beam_step: the last workgroup to finish writes *pos_advance = t + 1 and leaves the ticket at zero. */
+int evk_sample_step(const float* logp, int32_t ld, int32_t V1, int32_t R, int32_t max_len, const int64_t* pos, int32_t eos, int32_t pad,
+                    int32_t block_rows, int32_t decoding_constraint, float temperature, int32_t method, float param, int64_t* seq,
+                    unsigned char* unfinished, int64_t* words, float* seq_logprobs, const float* uniforms, int64_t* pos_advance,
+                    int32_t* ticket, evk_stream_t stream);
 /* F.normalize(p=2, eps=1e-12) rows, f32 */
 int evk_l2norm_fwd(const float* x, float* y, float* nrm, int64_t rows, int32_t D, evk_stream_t stream);
 int evk_l2norm_bwd(const float* dy, const float* y, const float* nrm, float* dx, int64_t rows, int32_t D, evk_stream_t stream);
