@@ -279,6 +279,45 @@ int evk_trunk_num_pairs(const evk_trunk_cfg* cfg) {
   return n;
 }
 
+/* read-only view of the training plan: what make_plan laid out, nothing computed, no device memory touched */
+int evk_trunk_plan(const evk_trunk_cfg* cfg, int32_t N, int32_t H, int32_t W, evk_trunk_pair_view* pairs, int32_t n_pairs,
+                   evk_trunk_plan_view* plan) {
+  Plan P;
+  TRY(make_plan(cfg, N, H, W, P));
+  EVK_REQUIRE(pairs && plan, "trunk_plan: null argument");
+  EVK_REQUIRE(n_pairs == (int)P.pairs.size(), "trunk_plan: expected room for %d conv+bn pairs, got %d", (int)P.pairs.size(), n_pairs);
+  int blk = -1, role = 0;
+  for (size_t i = 0; i < P.pairs.size(); ++i) {
+    const Pair& pr = P.pairs[i];
+    evk_trunk_pair_view& v = pairs[i];
+    if (i == 0) { blk = -1; role = 0; }
+    else if (role == 0 || role == 4 || (role == 3 && !P.has_down[blk])) { ++blk; role = 1; }
+    else ++role;
+    v.g = pr.g; v.C = pr.C; v.block = blk; v.role = role; v.M = pr.M;
+    v.y = pr.y; v.z = pr.z; v.dy = pr.dy; v.stats = pr.stats; v.sums = pr.sums;
+    v.act_bytes = pr.M * pr.C * 2; v.stats_bytes = 6L * pr.C * 4; v.sums_bytes = 2L * pr.C * 4;
+    v.wflip = P.wflip[i]; v.wcls = P.wcls[i];
+    v.wcls_bytes = P.wcls[i] >= 0 ? (long)pr.g.Co * 9 * pr.g.Ci * 2 : 0;
+    v.wflip_bytes = P.wflip[i] >= 0 ? (long)pr.g.Co * pr.g.KH * pr.g.KW * pr.g.Ci * 2 : 0;
+  }
+  evk_trunk_plan_view& o = *plan;
+  o.n_pairs = (int)P.pairs.size(); o.n_blocks = (int)P.has_down.size();
+  o.xpad = P.xpad; o.xpad_bytes = (long)N * (H + 6) * (W + 8) * 4 * 2;
+  o.wp = P.wp; o.wp_bytes = 64 * 224 * 2;
+  o.dwp = P.dwp; o.dwp_bytes = 64 * 224 * 4;
+  const long pooled = (long)N * (H / 4) * (W / 4) * 64;
+  o.pooled = P.pooled; o.pooled_bytes = pooled * 2;
+  o.pool_idx = P.pool_idx; o.pool_idx_bytes = pooled;
+  for (int i = 0; i < 6; ++i) o.gbuf[i] = P.gbuf[i];
+  o.gbuf_bytes = P.gcap;
+  o.red = P.red; o.red_bytes = P.red_bytes;
+  o.slab = P.slab; o.slab_bytes = P.slab_bytes;
+  o.zeros = P.zeros; o.zeros_bytes = 2 * 2048 * 4;
+  o.part = P.part; o.part_bytes = P.part_bytes;
+  o.total = P.total;
+  return EVK_OK;
+}
+
 int evk_trunk_forward(const evk_trunk_cfg* cfg, const evk_trunk_layer* layers, int32_t n_layers, const float* images, int32_t N,
                       int32_t H, int32_t W, void* ws, int64_t ws_bytes, void* out, int32_t training, evk_stream_t stream) {
   Plan P;

@@ -58,6 +58,31 @@ class TrunkLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('w', 'dw', 'gamma', 'beta', 'running_mean', 'running_var', 'dgamma', 'dbeta')]
 
 
+class TrunkPairView(C.Structure):
+    """evk_trunk_pair_view: workspace offsets (bytes) of one conv + batch-norm pair"""
+    _fields_ = ([('g', ConvGeom)] + [(n, C.c_int32) for n in ('C', 'block', 'role', 'pad_')] +
+                [(n, C.c_int64) for n in ('M', 'y', 'z', 'dy', 'stats', 'sums', 'act_bytes', 'stats_bytes', 'sums_bytes', 'wflip', 'wflip_bytes',
+                                          'wcls', 'wcls_bytes')])
+
+
+class TrunkPlanView(C.Structure):
+    _fields_ = ([('n_pairs', C.c_int32), ('n_blocks', C.c_int32)] +
+                [(n, C.c_int64) for n in ('xpad', 'xpad_bytes', 'wp', 'wp_bytes', 'dwp', 'dwp_bytes', 'pooled', 'pooled_bytes', 'pool_idx',
+                                          'pool_idx_bytes')] +
+                [('gbuf', C.c_int64 * 6)] +
+                [(n, C.c_int64) for n in ('gbuf_bytes', 'red', 'red_bytes', 'slab', 'slab_bytes', 'zeros', 'zeros_bytes', 'part', 'part_bytes',
+                                          'total')])
+
+
+def trunk_plan(cfg, N, Hh, Ww):
+    """(pairs, plan) of evk_trunk_plan: the workspace layout of the native trunk runner for N images of Hh x Ww (host only)"""
+    n = lib.evk_trunk_num_pairs(C.byref(cfg))
+    pairs = (TrunkPairView * n)()
+    plan = TrunkPlanView()
+    check(lib.evk_trunk_plan(C.byref(cfg), N, Hh, Ww, pairs, n, C.byref(plan)), 'trunk_plan')
+    return pairs, plan
+
+
 _CTYPES = {'int': C.c_int32, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'float': C.c_float,
            'evk_stream_t': C.c_void_p}
 

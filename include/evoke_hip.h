@@ -316,6 +316,38 @@ typedef struct evk_trunk_layer {
 } evk_trunk_layer;
 int evk_trunk_num_pairs(const evk_trunk_cfg* cfg);
 int64_t evk_trunk_ws_bytes(const evk_trunk_cfg* cfg, int32_t N, int32_t H, int32_t W);   /* -1 on bad arguments */
+/* Read-only view of the workspace layout evk_trunk_forward / evk_trunk_backward use (the training plan): computes nothing and touches no
+ * device memory.  Every offset is in bytes from the start of `ws`, a multiple of 256; -1 = the plan has no such region.  pairs[] has
+ * evk_trunk_num_pairs(cfg) entries in the order of `layers`.  Between evk_trunk_forward and the end of evk_trunk_backward a pair keeps
+ *   y      [M][C] 16-bit: the raw convolution output            z   [M][C] 16-bit: relu?(y * scale + shift (+ identity))
+ *   dy     [M][C] 16-bit: the gradient w.r.t. y (backward)      sums [2][C] f32: sum_g, sum_gx of the batch-norm backward
+ *   stats  [6][C] f32: sum, sumsq (of the f32 convolution result over the M rows; train mode only), scale, shift (z = y * scale + shift),
+ *          mean, invstd (batch statistics in train mode, running statistics in eval mode)
+ * role: 0 the 7x7 stem (g unused), 1-3 conv1-conv3 of bottleneck `block`, 4 its downsample. */
+typedef struct evk_trunk_pair_view {
+  evk_conv_geom g;
+  int32_t C, block, role, pad_;
+  int64_t M;
+  int64_t y, z, dy, stats, sums;
+  int64_t act_bytes, stats_bytes, sums_bytes;      /* sizes of y / z / dy, of stats, of sums                                  */
+  int64_t wflip, wflip_bytes;                      /* flipped / transposed 16-bit weights of the data gradient, or -1 / 0    */
+  int64_t wcls, wcls_bytes;                        /* parity-class weights of a stride-2 3x3 data gradient, or -1 / 0        */
+} evk_trunk_pair_view;
+typedef struct evk_trunk_plan_view {
+  int32_t n_pairs, n_blocks;
+  int64_t xpad, xpad_bytes;                        /* packed image [N][H+6][W+8][4] 16-bit                                   */
+  int64_t wp, wp_bytes, dwp, dwp_bytes;            /* packed stem weight [64][7][8][4] 16-bit and its f32 gradient           */
+  int64_t pooled, pooled_bytes;                    /* max-pool output [N][H/4][W/4][64] 16-bit                               */
+  int64_t pool_idx, pool_idx_bytes;                /* its window tap kh * 3 + kw, one byte per element                       */
+  int64_t gbuf[6], gbuf_bytes;                     /* rotating block-level gradient buffers, gbuf_bytes each                 */
+  int64_t red, red_bytes;                          /* evk_colreduce_ws_bytes(2048)                                           */
+  int64_t slab, slab_bytes;                        /* split-K slabs of the weight gradients                                  */
+  int64_t zeros, zeros_bytes;                      /* 2 x 2048 f32 zeros (eval-mode batch-norm backward)                     */
+  int64_t part, part_bytes;                        /* partial statistics rows of the convolution / data-gradient epilogues   */
+  int64_t total;                                   /* = evk_trunk_ws_bytes                                                   */
+} evk_trunk_plan_view;
+int evk_trunk_plan(const evk_trunk_cfg* cfg, int32_t N, int32_t H, int32_t W, evk_trunk_pair_view* pairs, int32_t n_pairs,
+                   evk_trunk_plan_view* plan);
 /* images f32 NCHW [N][3][H][W] -> out bf16 NHWC [N][H/32][W/32][4*planes[3]]; ws keeps what the backward needs */
 int evk_trunk_forward(const evk_trunk_cfg* cfg, const evk_trunk_layer* layers, int32_t n_layers, const float* images, int32_t N,
                       int32_t H, int32_t W, void* ws, int64_t ws_bytes, void* out, int32_t training, evk_stream_t stream);

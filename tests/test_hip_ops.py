@@ -945,6 +945,193 @@ def test_native_trunk_matches_module_walk():
         print('   native trunk vs module walk (train=%s): out %.3g, worst grad %.3g' % (train, e_out, worst))
 
 
+AUDIT_CASES = {
+    # blocks, planes, N, H, W, ill-conditioned batch-norm parameters.  96 x 160 images: no M is a multiple of a tile (layer4 has 3 x 5 pixels per
+    # image), N in {1, 3, 5}; (2,1,2,1) gives layers with a following block behind the strided / shortcut one; the narrow trunk makes a channel
+    # group of 8 a whole block of the batch-norm kernels
+    'b1111_p64_n5': ((1, 1, 1, 1), (64, 128, 256, 512), 5, 96, 160, False),
+    'b2121_p64_n3': ((2, 1, 2, 1), (64, 128, 256, 512), 3, 96, 160, False),
+    'b2121_p16_n1': ((2, 1, 2, 1), (16, 32, 64, 128), 1, 96, 160, False),
+    'b2121_p64_n3_ill': ((2, 1, 2, 1), (64, 128, 256, 512), 3, 64, 96, True),
+    # the full depth: 23 blocks of layer3 behind one another (the skip-chain budget), 104 pairs
+    'resnet101_n3_224': ((3, 4, 23, 3), (64, 128, 256, 512), 3, 224, 224, False),
+    'resnet101_n2_384': ((3, 4, 23, 3), (64, 128, 256, 512), 2, 384, 384, False),
+}
+NAN_FILL = 0x7FC0          # a quiet NaN as a 16-bit lane of either storage format, and (0x7FC07FC0) as an f32 lane
+
+
+def _same_bits(a, b, what):
+    bad = []
+    for k in a:
+        x, y = a[k], b[k]
+        if x is None and y is None:
+            continue
+        if not torch.equal(x.contiguous().view(-1).view(torch.uint8), y.contiguous().view(-1).view(torch.uint8)):
+            bad.append(k)
+    assert not bad, '%s: not bit-identical: %s' % (what, bad[:12])
+
+
+def _run_bits(TA, case, res, training=True):
+    """everything a run produced, keyed by name, for bit comparisons"""
+    out = dict(TA.stored_tensors(case.workspace(res['ws']), training=training))
+    out['out'] = res['out']
+    for i, g in enumerate(res['grads']):
+        for k, v in g.items():
+            out['pair%d.%s' % (i, k)] = v
+    for i, (a, b) in enumerate(res['running']):
+        out['pair%d.running_mean' % i], out['pair%d.running_var' % i] = a, b
+    return out
+
+
+@pytest.mark.parametrize('training', [True, False], ids=['train', 'eval'])
+@pytest.mark.parametrize('name', list(AUDIT_CASES))
+def test_native_trunk_matches_module_walk_hop_by_hop_in_fp64(name, training):
+    """evk_trunk_forward + evk_trunk_backward through ctypes on a workspace this test owns, audited hop by hop against float64
+    (tests/trunk_audit.py: every pair's y, statistics, z, dy, backward sums, parameter-gradient increments from non-zero starts, the stem's
+    packing, the max-pool and its recorded taps), with bounds derived from the number formats -- a few units of 16-bit round-off per hop,
+    not the 15 % / unbounded-gradient comparison of the end-to-end test above.  Workspace hygiene on the way: the workspace sits between two
+    1 MiB guard bands that must come back untouched, and a zero-filled and a NaN-filled workspace must give the same bits everywhere (a
+    difference means a kernel read workspace it never wrote); so must the backward with and without a separate weight-gradient stream (the
+    trunk's reductions are two-stage, no atomics), and freezing some parameters must not move the others."""
+    from evoke_amd import hip as H
+    from tests import trunk_audit as TA
+    torch.set_num_threads(min(torch.get_num_threads(), 16))
+    blocks, planes, N, Hh, Ww, ill = AUDIT_CASES[name]
+    case = TA.TrunkCase(blocks, planes, N, Hh, Ww, seed=len(name) + 7 * N, ill=ill)
+    if sum(blocks) > 8 and not training:
+        case.calibrate()
+    zero = case.run(training, 0, side_stream=True)
+    nan = case.run(training, NAN_FILL, side_stream=True)
+    one = case.run(training, NAN_FILL, side_stream=False)
+    for r, what in ((zero, 'zero fill'), (nan, 'NaN fill'), (one, 'NaN fill, one stream')):
+        assert r['guards_ok'], '%s: a guard band next to the workspace was written' % what
+    _same_bits(_run_bits(TA, case, zero, training), _run_bits(TA, case, nan, training), 'zero-filled against NaN-filled workspace')
+    _same_bits(_run_bits(TA, case, nan, training), _run_bits(TA, case, one, training), 'weight gradients on a second stream against one stream')
+    # frozen parameters: NULL gradient pointers on some pairs leave every other result unchanged bit for bit
+    npairs = len(case.pairs)
+    frozen = {(i, k) for i in range(0, npairs, 3) for k in ('dw',)} | {(i, k) for i in range(1, npairs, 4) for k in ('dgamma', 'dbeta')} | {(2, 'dw'), (2, 'dgamma'), (2, 'dbeta')}
+    part = case.run(training, NAN_FILL, side_stream=True, frozen=frozen)
+    assert part['guards_ok']
+    _same_bits({k: v for k, v in _run_bits(TA, case, part, training).items() if v is not None}, _run_bits(TA, case, nan, training), 'partially frozen against fully trainable')
+    fails, lines, _ = TA.evaluate(case.audit(nan, training))
+    print('   trunk audit %s (%s, %s storage): worst error / bound per pair' % (name, 'train' if training else 'eval', H.STORE))
+    print('\n'.join(lines))
+    assert not fails, '%d quantities outside their bounds:\n%s' % (len(fails), '\n'.join(fails[:30]))
+
+
+def test_resnet101_at_the_bench_geometry_hop_by_hop_in_fp64():
+    """The same audit at the benchmark's geometry -- resnet101, 64 images of 384 x 384, train mode -- where the host-side routing picks the
+    kernels the benchmark runs (it depends on M: halo-tile 3x3 forward / data / weight gradients, strip GEMM, weight-stationary pointwise
+    kernels with fused statistics, the halo stem, the folded second reduction stage), which the reduced cases do not all reach.  Default
+    build's pass only (the name keeps it out of the bf16 child and of the fallback-route child).  The 20 GB workspace is audited where it is:
+    float64 on the device, restricted to matmuls, slices, elementwise operations and reductions (tests/trunk_audit.py: conv_mm; data and
+    weight gradients by autograd over it) -- never the library under test, never a vendor convolution.  That device-side reference is first
+    validated against the CPU float64 restatement on a reduced case: the two must agree to a 10^-6 of each bound."""
+    from evoke_amd import hip as H
+    from tests import trunk_audit as TA
+    torch.set_num_threads(min(torch.get_num_threads(), 16))
+    small = TA.TrunkCase((2, 1, 2, 1), (64, 128, 256, 512), 3, 96, 160, seed=41)
+    res = small.run(True, NAN_FILL)
+    res_dev = dict(res, ws=res['ws'].cuda())
+    n = 0
+    for a, b in zip(small.audit(res, True), small.audit(res_dev, True)):
+        assert (a.pair, a.name) == (b.pair, b.name)
+        wa, wb, ba, bb = a.want.double(), b.want.double().cpu(), a.bound.double(), b.bound.double().cpu()
+        assert bool(((wa - wb).abs() <= 1e-6 * ba + 1e-13 * wa.abs()).all()), ('device reference differs from the CPU restatement', a.pair, a.name)
+        assert bool(((ba - bb).abs() <= 1e-6 * ba).all()), ('device bound differs from the CPU restatement', a.pair, a.name)
+        n += 1
+    assert n > 20 * 12
+    del res, res_dev, small
+    case = TA.TrunkCase((3, 4, 23, 3), (64, 128, 256, 512), 64, 384, 384, seed=64)
+    res = case.run(True, NAN_FILL, on_device=True)
+    assert res['guards_ok'], 'a guard band next to the workspace was written'
+    fails, lines, _ = TA.evaluate(case.audit(res, True))
+    print('   trunk audit resnet101 64 x 384 x 384 (train, %s storage): worst error / bound per pair' % H.STORE)
+    print('\n'.join(lines))
+    assert not fails, '%d quantities outside their bounds:\n%s' % (len(fails), '\n'.join(fails[:30]))
+
+
+def test_native_trunk_matches_module_walk_on_a_leased_poisoned_workspace():
+    """The product path (ResNetTrunk -> _TrunkFn -> the _WsLease pool) on a pool buffer this test seeded: NaN-filled, between guard bands.  Its
+    output, parameter gradients and running statistics equal, bit for bit, those of the ctypes calls on a zero-filled workspace of the test's
+    own; the guard bands come back untouched."""
+    import ctypes as C
+    from evoke_amd import hip as H
+    from evoke_amd import ops, trunk as T
+    from tests import trunk_audit as TA
+    torch.manual_seed(5)
+    ops.clear_grad_callbacks()
+    net = T.ResNetTrunk().cuda().train()
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, T.Bottleneck):
+                m.bn3.weight.mul_(0.2)
+    N, Hh, Ww = 2, 64, 96
+    img = torch.randn(N, 3, Hh, Ww, device='cuda')
+    dout = (torch.randn(N, Hh // 32, Ww // 32, 2048, device='cuda') * 0.1).to(BF)
+    cfg = net.native_cfg()
+    nb = H.lib.evk_trunk_ws_bytes(C.byref(cfg), N, Hh, Ww)
+    assert nb > 0
+    pairs = net.pairs()
+    running0 = [(bn.running_mean.clone(), bn.running_var.clone()) for _, bn in pairs]
+
+    def guarded(fill):
+        big = torch.full((2 * TA.GUARD + nb,), TA.GUARD_BYTE, dtype=torch.uint8, device='cuda')
+        assert big.data_ptr() % 256 == 0
+        big[TA.GUARD:TA.GUARD + nb].view(torch.int16).fill_(fill)
+        return big
+
+    def guards_ok(big):
+        return bool((big[:TA.GUARD] == TA.GUARD_BYTE).all()) and bool((big[TA.GUARD + nb:] == TA.GUARD_BYTE).all())
+
+    big = guarded(NAN_FILL)
+    key = (torch.cuda.current_device(), int(nb))
+    saved_pool = T._WsLease._pool.pop(key, None)
+    T._WsLease._pool[key] = [big[TA.GUARD:TA.GUARD + nb]]
+    try:
+        out = net(img)
+        out.backward(dout)
+        ops.join_side_streams()
+        torch.cuda.synchronize()
+        leased = T._WsLease._pool.get(key) or []
+        assert not leased or leased[0].data_ptr() == big.data_ptr() + TA.GUARD          # the seeded buffer was the one used and came back
+    finally:
+        T._WsLease._pool.pop(key, None)
+        if saved_pool is not None:
+            T._WsLease._pool[key] = saved_pool
+    assert guards_ok(big)
+    got = {'out': out.detach().clone()}
+    for i, (cv, bn) in enumerate(pairs):
+        got['pair%d.dw' % i], got['pair%d.dgamma' % i], got['pair%d.dbeta' % i] = cv.weight.grad.clone(), bn.weight.grad.clone(), bn.bias.grad.clone()
+        got['pair%d.running_mean' % i], got['pair%d.running_var' % i] = bn.running_mean.clone(), bn.running_var.clone()
+    ws_product = big[TA.GUARD:TA.GUARD + nb].cpu()
+    # the same step through ctypes: gradients and running statistics back to their starting values, a zero-filled workspace
+    with torch.no_grad():
+        for (cv, bn), (rm, rv) in zip(pairs, running0):
+            cv.weight.grad.zero_(); bn.weight.grad.zero_(); bn.bias.grad.zero_()
+            bn.running_mean.copy_(rm); bn.running_var.copy_(rv)
+    arr, keep = T._TrunkFn._layers(pairs, True)
+    big2 = guarded(0)
+    ws2 = big2[TA.GUARD:TA.GUARD + nb]
+    out2 = torch.empty_like(out)
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    H.check(H.lib.evk_trunk_forward(C.byref(cfg), arr, len(pairs), H.ptr(img), N, Hh, Ww, H.ptr(ws2), nb, H.ptr(out2), 1, H.stream()), 'trunk_forward')
+    H.check(H.lib.evk_trunk_backward(C.byref(cfg), arr, len(pairs), N, Hh, Ww, H.ptr(ws2), nb, H.ptr(dout), 1, H.stream(), side.cuda_stream), 'trunk_backward')
+    side.synchronize()
+    torch.cuda.synchronize()
+    assert guards_ok(big2)
+    want = {'out': out2}
+    for i, (cv, bn) in enumerate(pairs):
+        want['pair%d.dw' % i], want['pair%d.dgamma' % i], want['pair%d.dbeta' % i] = cv.weight.grad, bn.weight.grad, bn.bias.grad
+        want['pair%d.running_mean' % i], want['pair%d.running_var' % i] = bn.running_mean, bn.running_var
+    _same_bits({k: v.cpu() for k, v in got.items()}, {k: v.cpu() for k, v in want.items()}, 'product path against ctypes run')
+    # and everything the runner keeps in the workspace
+    pv, plan = H.trunk_plan(cfg, N, Hh, Ww)
+    a, b = TA.Workspace(ws_product, pv, plan, H.STORE_DTYPE), TA.Workspace(ws2.cpu(), pv, plan, H.STORE_DTYPE)
+    _same_bits(TA.stored_tensors(a), TA.stored_tensors(b), 'leased NaN-filled workspace against zero-filled workspace')
+
+
 def test_decode_attention_matches_reference():
     """evk_decode_attention (one query per row, whole K/V cache, key mask) against fp32 torch on the same bf16 inputs."""
     import ctypes as C

@@ -37,7 +37,10 @@ GRAD_TOL = 0.10 if F16 else 0.4
 PT_GRAD_TOL = 0.15 if F16 else 0.4
 # train-mode gradients (round 5: batch statistics in all 104 batch norms, i.e. the backward through the statistics as well): measured on the 67
 # tensors of ft224_inc -- cosine >= 0.963 (the stem and the first bottlenecks: 0.963-0.98; everything outside the trunk >= 0.998), energy
-# <= 4.1 % except the stem batch norm's bias (18 %: a 64-element vector at the end of 104 normalised layers)
+# <= 4.1 % except the stem batch norm's bias (18 %).  The hop-by-hop float64 audit (tests/trunk_audit.py, DESIGN.md "Parity") shows where the 18 %
+# comes from: the stem's own hop -- max-pool backward, ReLU gate, the column sum that IS this gradient -- is at 0.00-0.14 of its round-off bound
+# from the gradient the engine hands it, in both builds and on the fallback routes, as is every hop before it; what differs from the fp32
+# reference is the gradient that arrives there after 104 normalised layers (amplification along the chain, not a defect of a kernel)
 TRAIN_GRAD_TOL, TRAIN_GRAD_COS = (0.25, 0.95) if F16 else (0.6, 0.4)
 GRAD_COS = 0.975 if F16 else 0.5          # 66 tensors x 5 cases since round 3: measured 300 of 301 comparisons >= 0.99, the lowest 0.979
 
