@@ -30,13 +30,67 @@ struct BeamP {
   long long* pos_out; int* ticket;    // advance: the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
 };
 
-__global__ __launch_bounds__(256) void beam_step_kernel(const BeamP p) {
+// What evk_beam_step_opts adds (caption_model.py:148-150 previous-word constraint, :181-188 + :199 the sorted list of finished beams under
+// utils.penalty_builder, :84-99 the log-probability rows every decision was taken from).  The kernels are templates over OPTS: the
+// instantiation behind evk_beam_step carries none of this, neither as code nor as kernel arguments.
+struct BeamOpts {
+  int constraint, pad, R;             // mask the previous word's column at pos > 0; [PAD] id; R = B * beam rows of one history slab
+  const double* len_div;              // [max_len] or null: list score = running sum / len_div[pos] (f64), null = the running sum itself
+  double* fin_score; int* fin_len;    // [B][beam] finished list: score descending (ties: earlier entry first), length (0 = empty slot)
+  long long* fin_seq; int* fin_anc;   // [B][beam][max_len] words (padded with `pad`) and, per position, the row that scored it (or null)
+  float* hist;                        // [max_len][R][V1] or null: the rows of position pos as this step scanned them
+};
+template <bool OPTS> struct BeamArgs : BeamP {};
+template <> struct BeamArgs<true> : BeamP { BeamOpts o; };
+
+// the finished hypotheses of this step enter the study's list (thread 0 ranks, then every thread moves its columns of the list's rows:
+// entries only move DOWN, so walking the slots from the bottom up lets a thread read a column before it overwrites it -- no staging)
+__device__ __forceinline__ void finished_list_insert(const BeamP& p, const BeamOpts& o, int b, int tid, long pos, const float* win_v,
+                                                     const int* win_i, const long long* l_seq, const int* l_anc) {
+  __shared__ double f_sc[KMAX]; __shared__ int f_ln[KMAX]; __shared__ int f_src[KMAX];
+  const int n = p.beam;
+  if (tid == 0) {
+    for (int k = 0; k < n; ++k) { f_sc[k] = o.fin_score[b * n + k]; f_ln[k] = o.fin_len[b * n + k]; f_src[k] = k; }
+    const double div = (o.len_div && pos >= 0 && pos < p.max_len) ? o.len_div[pos] : 1.0;
+    for (int j = 0; j < n; ++j) {
+      if (!(p.force_end || win_i[j] % p.V1 == p.eos)) continue;
+      const double s = o.len_div ? (double)win_v[j] / div : (double)win_v[j];
+      int k = 0;
+      while (k < n && f_ln[k] != 0 && !(s > f_sc[k])) ++k;
+      if (k >= n) continue;
+      for (int q = n - 1; q > k; --q) { f_sc[q] = f_sc[q - 1]; f_ln[q] = f_ln[q - 1]; f_src[q] = f_src[q - 1]; }
+      f_sc[k] = s; f_ln[k] = (int)pos + 1; f_src[k] = n + j;
+    }
+    for (int k = 0; k < n; ++k) { o.fin_score[b * n + k] = f_sc[k]; o.fin_len[b * n + k] = f_ln[k]; }
+  }
+  __syncthreads();
+  for (int c = tid; c < p.max_len; c += 256)
+    for (int d = n - 1; d >= 0; --d) {
+      const int s = f_src[d];
+      if (s == d) continue;
+      long long w; int a = 0;
+      if (s < n) {
+        w = o.fin_seq[(long)(b * n + s) * p.max_len + c];
+        if (o.fin_anc) a = o.fin_anc[(long)(b * n + s) * p.max_len + c];
+      } else {
+        const int sb = win_i[s - n] / p.V1;
+        w = c < pos ? l_seq[sb * p.max_len + c] : c == pos ? (long long)(win_i[s - n] % p.V1) : (long long)o.pad;
+        a = c < pos ? ((l_anc && c < p.anc_cols) ? l_anc[sb * p.anc_cols + c] : b * n) : c == pos ? b * n + sb : 0;
+      }
+      o.fin_seq[(long)(b * n + d) * p.max_len + c] = w;
+      if (o.fin_anc) o.fin_anc[(long)(b * n + d) * p.max_len + c] = a;
+    }
+}
+
+template <bool OPTS>
+__global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs<OPTS> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float s_val[4]; __shared__ int s_idx[4];
   __shared__ float win_v[KMAX]; __shared__ int win_i[KMAX];
   __shared__ int s_best;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int beam = p.beam;
+  const long pos = p.pos[0];
   // ---- 1. top-`beam` candidates
   float bv[KMAX]; int bi[KMAX];
 #pragma unroll
@@ -48,10 +102,23 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamP p) {
   for (int src = 0; src < beam; ++src) {
     const float base = p.beam_sum[b * beam + src];
     const float* row = p.logp + (long)(b * beam + src) * p.ld;
+    int prev = -1; float* hrow = nullptr;
+    if constexpr (OPTS) {
+      if (p.o.constraint && pos > 0 && pos < p.max_len) prev = (int)p.beam_seq[((long)b * beam + src) * p.max_len + pos - 1];
+      if (p.o.hist && pos >= 0 && pos < p.max_len) hrow = p.o.hist + ((long)pos * p.o.R + b * beam + src) * p.V1;
+    }
     for (int w0 = tid; w0 < p.V1; w0 += 256 * UNR) {
       float lv[UNR];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) { const int w = w0 + 256 * u; lv[u] = w < p.V1 ? row[w] : 0.f; }
+      if constexpr (OPTS) {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          const int w = w0 + 256 * u;
+          if (w == prev) lv[u] = -INFINITY;
+          if (hrow && w < p.V1) hrow[w] = lv[u];
+        }
+      }
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         const int w = w0 + 256 * u;
@@ -86,7 +153,6 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamP p) {
     }
   }
   // ---- 2. stage the sample's rows, rewrite them in the winners' order
-  const long pos = p.pos[0];
   long long* seq = p.beam_seq + (long)b * beam * p.max_len;
   long long* l_seq = reinterpret_cast<long long*>(smem);                               // [beam][max_len]
   int* l_anc = reinterpret_cast<int*>(l_seq + (size_t)beam * p.max_len);               // [beam][anc_cols]
@@ -146,6 +212,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamP p) {
     for (int c = tid; c < p.max_len; c += 256)
       p.best_seq[(long)b * p.max_len + c] = c == pos ? (long long)(win_i[j] % p.V1) : l_seq[src * p.max_len + c];
   }
+  if constexpr (OPTS) finished_list_insert(p, p.o, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
   if (p.pos_out) {
     // the next decoder step writes its keys / values at position pos + 1 of every hypothesis's OWN cache row: seed that column of the row
     // table here (it replaces an index_copy launch), then let the last workgroup advance the position (it replaces an add launch)
@@ -191,7 +258,8 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
   v = bv; i = bi;
 }
 
-__global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamP p) {
+template <bool OPTS>
+__global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamArgs<OPTS> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float c_val[KMAX * KMAX]; __shared__ int c_idx[KMAX * KMAX];
   __shared__ float win_v[KMAX]; __shared__ int win_i[KMAX];
@@ -213,6 +281,20 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamP p) {
     const float* row = p.logp + (long)(b * beam + min(src, beam - 1)) * p.ld;
 #pragma unroll
     for (int i = 0; i < CMAX; ++i) { const int c = lane + 64 * i; x[u][i] = (src < beam && c < V1) ? row[c] : -INFINITY; }
+    if constexpr (OPTS) {
+      // the previous word's column is masked and the row goes to the history as it is scanned (no launch, one more write stream)
+      if (src < beam) {
+        int prev = -1;
+        if (p.o.constraint && pos > 0 && pos < p.max_len) prev = (int)seq[(long)src * p.max_len + pos - 1];
+        float* hrow = (p.o.hist && pos >= 0 && pos < p.max_len) ? p.o.hist + ((long)pos * p.o.R + b * beam + src) * V1 : nullptr;
+#pragma unroll
+        for (int i = 0; i < CMAX; ++i) {
+          const int c = lane + 64 * i;
+          if (c == prev) x[u][i] = -INFINITY;
+          if (hrow && c < V1) hrow[c] = x[u][i];
+        }
+      }
+    }
   }
   float base[2];
 #pragma unroll
@@ -322,6 +404,7 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamP p) {
     for (int c = tid; c < p.max_len; c += 256)
       p.best_seq[(long)b * p.max_len + c] = c == pos ? (long long)(win_i[j] % V1) : l_seq[src * p.max_len + c];
   }
+  if constexpr (OPTS) finished_list_insert(p, p.o, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
   if (p.pos_out) {
     if (p.anc && pos + 1 < p.anc_cols && tid < beam) p.anc[(long)(b * beam + tid) * p.anc_cols + pos + 1] = b * beam + tid;
     __syncthreads();
@@ -332,6 +415,55 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamP p) {
   }
 }
 
+// out[b * take + k][t][:] = hist[t][fin_anc[b][k][t]][:] for t < fin_len[b][k], zeros beyond: the seqLogprobs rows of the returned
+// hypotheses (att_model.py:131 / :135), read once after the search.  Pure copy: one workgroup per (position, output row).
+struct GatherP { const float* hist; const int* fin_anc; const int* fin_len; float* out; int beam, take, max_len, V1, R; };
+__global__ __launch_bounds__(256) void beam_gather_kernel(const GatherP p) {
+  const int t = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+  const int e = (row / p.take) * p.beam + row % p.take;               // list entry
+  const int a = p.fin_anc[(long)e * p.max_len + t];
+  const bool live = t < p.fin_len[e] && a >= 0 && a < p.R;
+  float* dst = p.out + ((long)row * p.max_len + t) * p.V1;
+  const float* src = p.hist + ((long)t * p.R + (live ? a : 0)) * p.V1;
+  if ((p.V1 & 3) == 0) {                                              // every row starts on a 16-byte boundary
+    const int n4 = p.V1 >> 2;
+    for (int i = tid; i < n4; i += 256) reinterpret_cast<float4*>(dst)[i] = live ? reinterpret_cast<const float4*>(src)[i] : float4{0.f, 0.f, 0.f, 0.f};
+  } else {
+    for (int i0 = tid; i0 < p.V1; i0 += 256 * 4) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const int i = i0 + 256 * u; v[u] = (live && i < p.V1) ? src[i] : 0.f; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const int i = i0 + 256 * u; if (i < p.V1) dst[i] = v[u]; }
+    }
+  }
+}
+
+int launch_beam_step(const BeamP& p, const BeamOpts* o, int B, hipStream_t s, const char* what) {
+  EVK_REQUIRE(p.logp && p.pos && p.beam_sum && p.beam_seq && p.best_p && p.best_seq && p.words && B > 0 && p.V1 > 0 && p.ld >= p.V1 && p.max_len > 0,
+              "%s: bad args", what);
+  EVK_REQUIRE(p.beam >= 1 && p.beam <= KMAX && p.beam <= p.V1, "%s: beam must be in [1, %d]", what, KMAX);
+  EVK_REQUIRE((!p.mem || (p.mem_row > 0 && p.mem_row % 2 == 0)) && (!p.anc || p.anc_cols > 0), "%s: bad state geometry", what);
+  EVK_REQUIRE(!p.pos_out || p.ticket, "%s: advancing the position needs a (zero-initialised) ticket word", what);
+  EVK_REQUIRE(!p.mem2 || p.mem, "%s: mem2 needs mem", what);
+  static const int fast_on = evk_tunable("EVK_BEAM_STEP_FAST", 1);
+  const bool fast = fast_on && p.V1 <= CMAX * 64;
+  const size_t lds = (size_t)p.beam * p.max_len * 8 + (p.anc ? (size_t)p.beam * p.anc_cols * 4 : 0) + (p.mem ? (size_t)p.beam * p.mem_row * 2 : 0) +
+                     (fast && p.mem2 ? (size_t)p.beam * p.mem_row * 2 : 0);
+  EVK_REQUIRE(lds <= 60000, "%s: %zu bytes of per-sample state do not fit the staging buffer", what, lds);
+  ProfScope ps(EVK_FAM_NORM, s);
+  if (o) {
+    BeamArgs<true> a; static_cast<BeamP&>(a) = p; a.o = *o;
+    if (fast) hipLaunchKernelGGL(beam_step_fast_kernel<true>, dim3(B), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(beam_step_kernel<true>, dim3(B), dim3(256), lds, s, a);
+  } else {
+    BeamArgs<false> a; static_cast<BeamP&>(a) = p;
+    if (fast) hipLaunchKernelGGL(beam_step_fast_kernel<false>, dim3(B), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(beam_step_kernel<false>, dim3(B), dim3(256), lds, s, a);
+  }
+  return evk_check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,24 +471,36 @@ extern "C" {
 int evk_beam_step(const float* logp, int32_t ld, int32_t V1, int32_t beam, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
                   int32_t force_end, float* beam_sum, int64_t* beam_seq, float* best_p, int64_t* best_seq, int64_t* words, void* mem,
                   int32_t mem_row, int32_t* anc, int32_t anc_cols, int64_t* pos_advance, int32_t* ticket, void* mem2, evk_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  EVK_REQUIRE(logp && pos && beam_sum && beam_seq && best_p && best_seq && words && B > 0 && V1 > 0 && ld >= V1 && max_len > 0, "beam_step: bad args");
-  EVK_REQUIRE(beam >= 1 && beam <= KMAX && beam <= V1, "beam_step: beam must be in [1, %d]", KMAX);
-  EVK_REQUIRE((!mem || (mem_row > 0 && mem_row % 2 == 0)) && (!anc || anc_cols > 0), "beam_step: bad state geometry");
-  EVK_REQUIRE(!pos_advance || ticket, "beam_step: advancing the position needs a (zero-initialised) ticket word");
-  EVK_REQUIRE(!mem2 || mem, "beam_step: mem2 needs mem");
-  static const int fast_on = evk_tunable("EVK_BEAM_STEP_FAST", 1);
-  const bool fast = fast_on && V1 <= CMAX * 64;
-  const size_t lds = (size_t)beam * max_len * 8 + (anc ? (size_t)beam * anc_cols * 4 : 0) + (mem ? (size_t)beam * mem_row * 2 : 0) +
-                     (fast && mem2 ? (size_t)beam * mem_row * 2 : 0);
-  EVK_REQUIRE(lds <= 60000, "beam_step: %zu bytes of per-sample state do not fit the staging buffer", lds);
   BeamP p{logp, ld, V1, beam, max_len, eos, force_end, reinterpret_cast<const long long*>(pos), beam_sum, reinterpret_cast<long long*>(beam_seq),
           best_p, reinterpret_cast<long long*>(best_seq), reinterpret_cast<long long*>(words), (bf16_t*)mem, mem_row, anc, anc_cols,
           (bf16_t*)mem2, reinterpret_cast<long long*>(pos_advance), ticket};
+  return launch_beam_step(p, nullptr, B, reinterpret_cast<hipStream_t>(stream), "beam_step");
+}
+
+int evk_beam_step_opts(const float* logp, int32_t ld, int32_t V1, int32_t beam, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                       int32_t force_end, float* beam_sum, int64_t* beam_seq, float* best_p, int64_t* best_seq, int64_t* words, void* mem,
+                       int32_t mem_row, int32_t* anc, int32_t anc_cols, int64_t* pos_advance, int32_t* ticket, void* mem2, int32_t pad,
+                       int32_t decoding_constraint, const double* len_div, double* fin_score, int32_t* fin_len, int64_t* fin_seq,
+                       int32_t* fin_anc, float* hist, evk_stream_t stream) {
+  EVK_REQUIRE(fin_score && fin_len && fin_seq, "beam_step_opts: the finished list (score, length, sequence) is required");
+  EVK_REQUIRE(B > 0 && beam >= 1 && (int64_t)B * beam <= INT32_MAX / 2, "beam_step_opts: bad args");
+  BeamP p{logp, ld, V1, beam, max_len, eos, force_end, reinterpret_cast<const long long*>(pos), beam_sum, reinterpret_cast<long long*>(beam_seq),
+          best_p, reinterpret_cast<long long*>(best_seq), reinterpret_cast<long long*>(words), (bf16_t*)mem, mem_row, anc, anc_cols,
+          (bf16_t*)mem2, reinterpret_cast<long long*>(pos_advance), ticket};
+  BeamOpts o{decoding_constraint != 0, pad, B * beam, len_div, fin_score, fin_len, reinterpret_cast<long long*>(fin_seq), fin_anc, hist};
+  return launch_beam_step(p, &o, B, reinterpret_cast<hipStream_t>(stream), "beam_step_opts");
+}
+
+int evk_beam_gather_logprobs(const float* hist, const int32_t* fin_anc, const int32_t* fin_len, float* out, int32_t B, int32_t beam,
+                             int32_t take, int32_t max_len, int32_t V1, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(hist && fin_anc && fin_len && out && B > 0 && V1 > 0 && max_len > 0, "beam_gather_logprobs: bad args");
+  EVK_REQUIRE(beam >= 1 && beam <= KMAX && take >= 1 && take <= beam, "beam_gather_logprobs: take must be in [1, beam], beam in [1, %d]", KMAX);
+  EVK_REQUIRE((int64_t)B * take <= 65535, "beam_gather_logprobs: %lld output rows exceed the grid", (long long)B * take);
+  GatherP p{hist, fin_anc, fin_len, out, beam, take, max_len, V1, B * beam};
   ProfScope ps(EVK_FAM_NORM, s);
-  if (fast) hipLaunchKernelGGL(beam_step_fast_kernel, dim3(B), dim3(256), lds, s, p);
-  else hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), lds, s, p);
-  return evk_check_launch("beam_step");
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(max_len, B * take), dim3(256), 0, s, p);
+  return evk_check_launch("beam_gather_logprobs");
 }
 
 }  // extern "C"

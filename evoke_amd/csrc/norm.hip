@@ -286,10 +286,11 @@ struct LsmP {
   const float* logits; float* logp; const long long* target; const float* wmask; float* acc2;  // acc2 = {sum(-logp*w), sum(w)}
   float* lse; long rows; int V, ld, ld_out;
   float* rownll;   // optional [rows]: -logp[target] * w per row instead of the atomic accumulation (summed by the caller: order-independent bits)
+  float scale;     // SCALED only: log_softmax(logits * scale) -- the beam search's temperature (caption_model.py:196), no target
 };
 // REG = true (V <= 24 * 64): the row is read ONCE into registers (one memory round trip; the three passes below re-read it from L2 each --
 // the decode step calls this once per generated token on 256 rows x 1445 and is latency bound)
-template <bool REG>
+template <bool REG, bool SCALED = false>
 __global__ __launch_bounds__(256) void logsoftmax_kernel(const LsmP p) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -299,7 +300,14 @@ __global__ __launch_bounds__(256) void logsoftmax_kernel(const LsmP p) {
   float xr[REG ? 24 : 1];
   if constexpr (REG) {
 #pragma unroll
-    for (int i = 0; i < 24; ++i) { const int c = lane + 64 * i; xr[i] = c < p.V ? in[c] : -INFINITY; mx = fmaxf(mx, xr[i]); }
+    for (int i = 0; i < 24; ++i) {
+      const int c = lane + 64 * i;
+      xr[i] = c < p.V ? in[c] : -INFINITY;
+      if constexpr (SCALED) xr[i] *= p.scale;
+      mx = fmaxf(mx, xr[i]);
+    }
+  } else if constexpr (SCALED) {
+    for (int c = lane; c < p.V; c += 64) mx = fmaxf(mx, in[c] * p.scale);
   } else {
     for (int c = lane; c < p.V; c += 64) mx = fmaxf(mx, in[c]);
   }
@@ -308,6 +316,8 @@ __global__ __launch_bounds__(256) void logsoftmax_kernel(const LsmP p) {
   if constexpr (REG) {
 #pragma unroll
     for (int i = 0; i < 24; ++i) s += (lane + 64 * i < p.V) ? __expf(xr[i] - mx) : 0.f;
+  } else if constexpr (SCALED) {
+    for (int c = lane; c < p.V; c += 64) s += __expf(in[c] * p.scale - mx);
   } else {
     for (int c = lane; c < p.V; c += 64) s += __expf(in[c] - mx);
   }
@@ -319,6 +329,8 @@ __global__ __launch_bounds__(256) void logsoftmax_kernel(const LsmP p) {
     if constexpr (REG) {
 #pragma unroll
       for (int i = 0; i < 24; ++i) { const int c = lane + 64 * i; if (c < p.V) o[c] = xr[i] - lse; }
+    } else if constexpr (SCALED) {
+      for (int c = lane; c < p.V; c += 64) o[c] = in[c] * p.scale - lse;
     } else {
       for (int c = lane; c < p.V; c += 64) o[c] = in[c] - lse;
     }
@@ -650,18 +662,30 @@ int evk_log_softmax_nll_fwd(const float* logits, float* logp, float* lse, const 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   EVK_REQUIRE(logits && rows > 0 && V > 0 && V <= ld, "log_softmax: bad args");
   EVK_REQUIRE(!target || (wmask && acc2), "log_softmax: NLL needs wmask and acc2");
-  LsmP p{logits, logp, (const long long*)target, wmask, acc2, lse, rows, V, ld, ld_out, nullptr};
+  LsmP p{logits, logp, (const long long*)target, wmask, acc2, lse, rows, V, ld, ld_out, nullptr, 1.f};
   ProfScope ps(EVK_FAM_NORM, s);
   if (V <= 24 * 64) hipLaunchKernelGGL(logsoftmax_kernel<true>, dim3(row_blocks(rows)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(logsoftmax_kernel<false>, dim3(row_blocks(rows)), dim3(256), 0, s, p);
   return evk_check_launch("log_softmax");
 }
 
+int evk_log_softmax_scaled(const float* logits, float* logp, int64_t rows, int32_t V, int32_t ld, int32_t ld_out, float scale,
+                           evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(logits && logp && rows > 0 && V > 0 && V <= ld && V <= ld_out, "log_softmax_scaled: bad args");
+  EVK_REQUIRE(scale > 0.f && scale < INFINITY, "log_softmax_scaled: the scale must be positive and finite");
+  LsmP p{logits, logp, nullptr, nullptr, nullptr, nullptr, rows, V, ld, ld_out, nullptr, scale};
+  ProfScope ps(EVK_FAM_NORM, s);
+  if (V <= 24 * 64) hipLaunchKernelGGL((logsoftmax_kernel<true, true>), dim3(row_blocks(rows)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((logsoftmax_kernel<false, true>), dim3(row_blocks(rows)), dim3(256), 0, s, p);
+  return evk_check_launch("log_softmax_scaled");
+}
+
 int evk_log_softmax_nll_rows(const float* logits, float* lse, const int64_t* target, const float* wmask, float* row_nll, int64_t rows,
                              int32_t V, int32_t ld, evk_stream_t stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   EVK_REQUIRE(logits && target && wmask && row_nll && rows > 0 && V > 0 && V <= ld, "log_softmax_nll_rows: bad args");
-  LsmP p{logits, nullptr, (const long long*)target, wmask, nullptr, lse, rows, V, ld, ld, row_nll};
+  LsmP p{logits, nullptr, (const long long*)target, wmask, nullptr, lse, rows, V, ld, ld, row_nll, 1.f};
   ProfScope ps(EVK_FAM_NORM, s);
   if (V <= 24 * 64) hipLaunchKernelGGL(logsoftmax_kernel<true>, dim3(row_blocks(rows)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(logsoftmax_kernel<false>, dim3(row_blocks(rows)), dim3(256), 0, s, p);

@@ -261,6 +261,7 @@ class _DecoderState:
         self.mem = model.rm.init_memory(R, enc.device)
         self.t = 0
         self.anc = self.rows = None      # cache row table of the graph-mode steps (step_static)
+        self.logit_scale = 1.0           # 1 / temperature of the beam search's later steps (step_static only; caption_model.py:196)
         self.tmem = None                 # tanh(memory), kept beside the memory by the session path (evk_rm_decode_step)
         # the f32 relational memory (evk_rm_decode_step_f32): the state, the unrounded token embedding, scratch, the 16-bit row for the decoder
         self.mem32 = self.emb32 = self.rm32_ws = self.rm32_out = None
@@ -434,7 +435,7 @@ class _DecoderState:
             nf = n_final if n_final is not None else fn(x).view(-1, d)
             ops.gemm(nf, ops.shadow(lg.weight, pad_rows=(V1 != Np)), self.logits_buf, x.shape[0], V1, d, lda=d, ldb=d, ldc=Np, bias=lg.bias)
             logits = self.logits_buf
-        return ops.log_softmax(logits.view(logits.shape[0], -1), self.dec.vocab_size + 1, out=out)
+        return ops.log_softmax(logits.view(logits.shape[0], -1), self.dec.vocab_size + 1, out=out, scale=self.logit_scale)
 
     def step(self, it):
         """it (R,) token ids at position self.t -> f32 log-probs (R, V+1) of the next token."""
@@ -644,12 +645,121 @@ class _Session:
         stats['fused_bookkeeping'] = True
 
 
+_warned = set()
+
+
+def _length_divisors(length_penalty, max_len):
+    """utils.penalty_builder (modules/utils.py:160-186) as a table: the modifier the running sum of a hypothesis of length t + 1 is divided
+    by, in Python floats as the reference computes it -> list of max_len floats, or None for '' (identity).  'avg_<x>': the length;
+    'wu_<a>': (5 + length)^a / 6^a.  Anything else is a ValueError (the reference returns None there and fails at the first finished beam)."""
+    if length_penalty == '':
+        return None
+    parts = str(length_penalty).split('_')
+    if len(parts) != 2 or parts[0] not in ('wu', 'avg'):
+        raise ValueError("length_penalty must be '', 'avg_<x>' or 'wu_<alpha>', not %r" % (length_penalty,))
+    try:
+        alpha = float(parts[1])
+    except ValueError:
+        raise ValueError("length_penalty must be '', 'avg_<x>' or 'wu_<alpha>', not %r" % (length_penalty,)) from None
+    if parts[0] == 'avg':
+        return [float(t) for t in range(1, max_len + 1)]
+    return [((5 + t) ** alpha) / ((5 + 1) ** alpha) for t in range(1, max_len + 1)]
+
+
+def beam_options(args, beam, return_logprobs=False):
+    """The options of CaptionModel.beam_search / AttModel._sample_beam read from `args` and validated -> None when every one is at its
+    default and no log-probabilities are asked for (the search then runs exactly the launches it always ran), else a dict (part of the
+    session key: the options are kernel arguments of the captured step)."""
+    if args.get('group_size', 1) != 1:
+        raise NotImplementedError("diverse beam search (group_size > 1) is not on the path: the reference's own grouped search fails "
+                                  '(CaptionModel.beam_search calls self.repeat_tensor, which no class defines), so there is nothing to match')
+    if args.get('suppress_UNK', 0) and 'suppress_UNK' not in _warned:
+        import warnings
+        _warned.add('suppress_UNK')
+        warnings.warn("suppress_UNK is inert: the reference applies it only when the model has a `vocab` attribute, which EncoderDecoder "
+                      'never has (caption_model.py:152); it has no effect here either')
+    n = int(args.get('sample_n', 1))
+    if n != 1 and n != beam:
+        raise ValueError('beam search: sample_n must be 1 or beam_size (%d), not %d' % (beam, n))
+    temperature = float(args.get('temperature', 1.0))
+    if not (temperature > 0 and math.isfinite(temperature)):
+        raise ValueError('temperature must be positive')
+    length_penalty = args.get('length_penalty', '') or ''
+    _length_divisors(length_penalty, 1)
+    opts = dict(temperature=temperature, decoding_constraint=int(bool(args.get('decoding_constraint', 0))), length_penalty=str(length_penalty),
+                sample_n=n, return_logprobs=bool(return_logprobs))
+    if opts == dict(temperature=1.0, decoding_constraint=0, length_penalty='', sample_n=1, return_logprobs=False):
+        return None
+    return opts
+
+
+class _BeamLists:
+    """What evk_beam_step_opts keeps beside the plain bookkeeping: per study the sorted list of finished hypotheses (score f64, length,
+    words, and per position the row whose log-probabilities scored it), the length-penalty table, and -- only when log-probabilities are
+    asked for -- the history of every step's rows (max_len x R x (V+1) f32: ~225 MB at 32 studies x beam 4 x 100 positions x 4.4 k words)."""
+
+    def __init__(self, dec, B, beam, max_len, dev, opts):
+        self.dec, self.B, self.beam, self.max_len, self.opts = dec, B, beam, max_len, opts
+        self.score = torch.empty(B, beam, dtype=torch.float64, device=dev)
+        self.len = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        self.seq = torch.empty(B, beam, max_len, dtype=torch.long, device=dev)
+        self.anc = torch.empty(B, beam, max_len, dtype=torch.int32, device=dev)
+        div = _length_divisors(opts['length_penalty'], max_len)
+        self.len_div = torch.tensor(div, dtype=torch.float64, device=dev) if div is not None else None
+        self.hist = torch.empty(max_len, B * beam, dec.vocab_size + 1, dtype=F32, device=dev) if opts['return_logprobs'] else None
+
+    def reset(self):
+        self.score.fill_(-float('inf'))
+        self.len.zero_()
+        self.seq.fill_(self.dec.pad_idx)
+        self.anc.zero_()
+
+    def result(self, return_scores):
+        """-> seq (rows, max_len) [, seq_logprobs (rows, max_len, V+1) f32] [, scores (rows,) f64], rows = B * sample_n, the entries of a
+        study next to each other in list order (att_model.py:126-135)"""
+        n, B, max_len, V1 = self.opts['sample_n'], self.B, self.max_len, self.dec.vocab_size + 1
+        out = [self.seq[:, :n].reshape(B * n, max_len).clone()]
+        if self.hist is not None:
+            slp = torch.empty(B * n, max_len, V1, dtype=F32, device=self.seq.device)
+            H.check(H.lib.evk_beam_gather_logprobs(H.ptr(self.hist), H.ptr(self.anc), H.ptr(self.len), H.ptr(slp), B, self.beam, n, max_len, V1,
+                                                   H.stream()), 'beam_gather_logprobs')
+            out.append(slp)
+        if return_scores:
+            out.append(self.score[:, :n].reshape(-1).clone())
+        return out[0] if len(out) == 1 else tuple(out)
+
+
+def _beam_step(dec, lp, beam, B, max_len, pos, last, beam_sum, beam_seq, best_p, best_seq, words, mem, mem_row, anc, pos_advance, ticket, mem2,
+               lists=None):
+    """one launch of csrc/beam.hip: evk_beam_step, or evk_beam_step_opts when the search carries options (`lists`)"""
+    head = (H.ptr(lp), lp.shape[-1], dec.vocab_size + 1, beam, B, max_len, H.ptr(pos), dec.eos_idx, int(last), H.ptr(beam_sum), H.ptr(beam_seq),
+            H.ptr(best_p), H.ptr(best_seq), H.ptr(words), H.ptr(mem), mem_row, H.ptr(anc), anc.shape[1] if anc is not None else 0,
+            H.ptr(pos_advance), H.ptr(ticket), H.ptr(mem2))
+    if lists is None:
+        H.check(H.lib.evk_beam_step(*head, H.stream()), 'beam_step')
+    else:
+        H.check(H.lib.evk_beam_step_opts(*head, dec.pad_idx, lists.opts['decoding_constraint'], H.ptr(lists.len_div), H.ptr(lists.score),
+                                         H.ptr(lists.len), H.ptr(lists.seq), H.ptr(lists.anc), H.ptr(lists.hist), H.stream()), 'beam_step_opts')
+
+
+def _beam_first_position(dec, logp0, beam, B, max_len, beam_sum, beam_seq, best_p, best_seq, words, lists):
+    """position 0 of a search with options through the same kernel, so that the finished list sees an [EOS] at position 0 and max_len == 1:
+    the study's one row stands in for all `beam` source rows, of which only the first has a finite running sum (-inf + logp never wins)"""
+    V1 = dec.vocab_size + 1
+    beam_sum.fill_(-float('inf'))
+    beam_sum[:, 0] = 0.0
+    lp0 = logp0.view(B, -1)[:, :V1].repeat_interleave(beam, 0).contiguous()
+    pos0 = torch.zeros(1, dtype=torch.long, device=lp0.device)
+    _beam_step(dec, lp0, beam, B, max_len, pos0, max_len == 1, beam_sum, beam_seq, best_p, best_seq, words, None, 0, None, None, None, None, lists)
+
+
 class _BeamSession(_Session):
     """The session of a beam search over B samples x `beam` hypotheses: the shared state plus the beam bookkeeping arrays."""
 
-    def __init__(self, dec, B, beam, max_len, S, dev, slot=0):
+    def __init__(self, dec, B, beam, max_len, S, dev, slot=0, opts=None):
         super().__init__(dec, B, B * beam, max_len, S, dev, slot)
         self.beam = beam
+        self.lists = _BeamLists(dec, B, beam, max_len, dev, opts) if opts is not None else None
         self.beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
         self.beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
         self.best_p = torch.empty(B, dtype=F32, device=dev)
@@ -659,18 +769,36 @@ class _BeamSession(_Session):
     def _book_kernel(self, last):
         """one launch (csrc/beam.hip): top-beam, sequence / cache-row-table / relational-memory reorder in place, finished-beam tracking,
         -1000 penalty, next input tokens -- and, between steps, the position counter's increment and the row table's next column"""
-        dec, st, lp = self.dec, self.st, self.logp_buf
-        H.check(H.lib.evk_beam_step(H.ptr(lp), lp.shape[-1], dec.vocab_size + 1, self.beam, self.B, self.max_len, H.ptr(self.pos), dec.eos_idx,
-                                    int(last), H.ptr(self.beam_sum), H.ptr(self.beam_seq), H.ptr(self.best_p), H.ptr(self.best_seq),
-                                    H.ptr(self.words), H.ptr(st.mem32 if st.mem32 is not None else st.mem),
-                                    st.mem[0].numel() * (2 if st.mem32 is not None else 1), H.ptr(st.anc), st.anc.shape[1],
-                                    None if last else H.ptr(self.pos), H.ptr(self.ticket), H.ptr(st.tmem) if st.mem32 is None else None,
-                                    H.stream()), 'beam_step')
+        st = self.st
+        _beam_step(self.dec, self.logp_buf, self.beam, self.B, self.max_len, self.pos, last, self.beam_sum, self.beam_seq, self.best_p, self.best_seq,
+                   self.words, st.mem32 if st.mem32 is not None else st.mem, st.mem[0].numel() * (2 if st.mem32 is not None else 1), st.anc,
+                   None if last else self.pos, self.ticket, st.tmem if st.mem32 is None else None, self.lists)
 
     def _body(self):
         """positions 1 .. max_len-2: bookkeeping at position `pos` (which also advances it), then the decoder step that writes pos + 1"""
         self._book_kernel(False)
         self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
+
+    def _first_position(self, logp0, hook):
+        """position 0 of the plain search, eagerly in torch (the hypothesis count grows from B to B * beam here) -> (word_ix, state_ix)"""
+        dec, B, beam, max_len = self.dec, self.B, self.beam, self.max_len
+        V1 = dec.vocab_size + 1
+        hook(0, logp0, self.beam_sum)
+        ys, ix = _topk(logp0.view(B, -1)[:, :V1].contiguous(), beam)
+        word_ix = ix % V1                                                   # one source hypothesis per sample: the flat index IS the word
+        state_ix = self.base.expand(B, beam).reshape(-1)                    # hypothesis r of sample b starts from sample b's state
+        self.beam_seq[:, :, 0] = word_ix
+        self.beam_sum.copy_(ys)
+        last = max_len == 1
+        is_end = torch.ones_like(word_ix, dtype=torch.bool) if last else (word_ix == dec.eos_idx)
+        p_end = torch.where(is_end, self.beam_sum, torch.full_like(self.beam_sum, -float('inf')))
+        pv, pi = p_end.max(dim=1)
+        better = pv > self.best_p
+        cand_seq = self.beam_seq.gather(1, pi.view(B, 1, 1).expand(-1, 1, max_len))[:, 0]
+        self.best_seq.copy_(torch.where(better.unsqueeze(1), cand_seq, self.best_seq))
+        self.best_p.copy_(torch.where(better, pv, self.best_p))
+        self.beam_sum.sub_(1000.0 * is_end.to(F32))
+        return word_ix, state_ix
 
     def _run_iter(self, enc, src_mask, return_scores=False, step_hook=None, burst=0):
         """run() as a generator that yields after every issued token step: a scheduler that drives several sessions (one per HIP stream)
@@ -692,21 +820,17 @@ class _BeamSession(_Session):
         self.beam_sum.zero_()
         self.best_p.fill_(-float('inf'))
         self.best_seq.fill_(dec.pad_idx)
-        hook(0, logp0, self.beam_sum)
-        ys, ix = _topk(logp0.view(B, -1)[:, :V1].contiguous(), beam)
-        word_ix = ix % V1                                                   # one source hypothesis per sample: the flat index IS the word
-        state_ix = self.base.expand(B, beam).reshape(-1)                    # hypothesis r of sample b starts from sample b's state
-        self.beam_seq[:, :, 0] = word_ix
-        self.beam_sum.copy_(ys)
-        last = max_len == 1
-        is_end = torch.ones_like(word_ix, dtype=torch.bool) if last else (word_ix == dec.eos_idx)
-        p_end = torch.where(is_end, self.beam_sum, torch.full_like(self.beam_sum, -float('inf')))
-        pv, pi = p_end.max(dim=1)
-        better = pv > self.best_p
-        cand_seq = self.beam_seq.gather(1, pi.view(B, 1, 1).expand(-1, 1, max_len))[:, 0]
-        self.best_seq.copy_(torch.where(better.unsqueeze(1), cand_seq, self.best_seq))
-        self.best_p.copy_(torch.where(better, pv, self.best_p))
-        self.beam_sum.sub_(1000.0 * is_end.to(F32))
+        if self.lists is not None:
+            self.lists.reset()
+            st.logit_scale = 1.0 / self.lists.opts['temperature']      # positions >= 1 only (att_model.py:119: position 0 is not scaled)
+            self.beam_sum.fill_(-float('inf'))
+            self.beam_sum[:, 0] = 0.0
+            hook(0, logp0, self.beam_sum)
+            _beam_first_position(dec, logp0, beam, B, max_len, self.beam_sum, self.beam_seq, self.best_p, self.best_seq, self.words, self.lists)
+            word_ix = self.words.view(B, beam).clone()
+            state_ix = self.base.expand(B, beam).reshape(-1)
+        else:
+            word_ix, state_ix = self._first_position(logp0, hook)
         if max_len > 1:
             # the B -> B*beam expansion: every hypothesis inherits its sample's memory and position-0 keys / values
             ops.copy_kernel(st.mem, st0.mem.index_select(0, state_ix).contiguous())
@@ -732,6 +856,8 @@ class _BeamSession(_Session):
             yield from self._drive(max_len - 2, 2, step_hook, burst, (self.beam_sum,))
             self._book_kernel(True)                                      # t = max_len - 1: every live beam is closed
             _reap_plans()
+        if self.lists is not None:
+            return self.lists.result(return_scores)
         seq = self.best_seq.clone()
         if return_scores:
             return seq, self.best_p.clone()
@@ -822,32 +948,39 @@ def _session_ok(dec, args, enc):
 
 
 @torch.no_grad()
-def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0):
-    """-> (B, max_seq_len) int64 token ids padded with [PAD] (= AttModel._sample_beam with sample_n = 1).
+def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, return_logprobs=False):
+    """AttModel._sample_beam (modules/att_model.py:98-137) -> seq (rows, max_seq_len) int64 token ids padded with [PAD]; with return_logprobs
+    (seq, seq_logprobs (rows, max_seq_len, V+1) f32: the log-probability row every word was selected from, after temperature and constraint,
+    zero beyond the hypothesis's length); with return_scores the list scores (rows,) come last (f32 running sums on the plain route, f64
+    after the length penalty once an option is set).  rows = B * sample_n.  Options read from `args` (beam_options): temperature (positions
+    >= 1), decoding_constraint, length_penalty ('' | 'avg_<x>' | 'wu_<alpha>'), sample_n (1: the best finished hypothesis of each study;
+    beam_size: all `beam_size` entries of its finished list, next to each other in list order).  With every option at its default and no
+    log-probabilities the search issues exactly the launches it issued before the options existed.
     step_hook(t, logp, beam_sum): test instrument, called on the launching stream right before the bookkeeping of position t consumes
     `logp` (f32, one row of >= V+1 log-probabilities per live hypothesis; may be edited in place) with the running sums (B, beam).
     slot: which of the decoder's persistent sessions to use (searches that are in flight at the same time need different slots);
     as_iterator: return a generator that yields after every issued token step and returns the result (see _BeamSession.run_iter);
     burst: with as_iterator, token steps per native call (see _BeamSession._run_iter)."""
+    beam, max_len = int(args.get('beam_size', 3)), int(args['max_seq_len'])
+    opts = beam_options(args, beam, return_logprobs)
+    if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
+        raise ValueError('beam_size must be in [1, 8]')
     if not _session_ok(dec, args, enc_states):
         if as_iterator:
             raise NotImplementedError('stepwise beam search needs the session path')
-        return _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores, step_hook)
+        return _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores, step_hook, return_logprobs)
     was_training = dec.training
     dec.eval()
     try:
-        beam, max_len = int(args.get('beam_size', 3)), int(args['max_seq_len'])
-        if args.get('group_size', 1) != 1 or args.get('sample_n', 1) != 1:
-            raise NotImplementedError('diverse beam search (group_size > 1) is not on the path')
-        if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
-            raise ValueError('beam_size must be in [1, 8]')
         enc, src_mask = dec.encode(enc_states, enc_mask)
         B, S, dev = enc.shape[0], enc.shape[1], enc.device
         key = (B, beam, max_len, S, dev.index, src_mask is None, slot)
+        if opts is not None:
+            key = key + (tuple(sorted(opts.items())),)
         sessions = _SESSIONS.setdefault(dec, {})
         ses = sessions.pop(key, None)
         if ses is None:
-            ses = _BeamSession(dec, B, beam, max_len, S, dev, slot)
+            ses = _BeamSession(dec, B, beam, max_len, S, dev, slot, opts)
             while len(sessions) >= 6:                   # a few batch geometries / slots at most (each holds its caches: 6 x R x max_len x 512 x 2 B)
                 sessions.pop(next(iter(sessions)))
         sessions[key] = ses
@@ -894,7 +1027,8 @@ def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=Non
     try:
         max_len, n = int(args['max_seq_len']), int(args.get('sample_n', 1))
         if args.get('group_size', 1) != 1:
-            raise NotImplementedError('diverse sampling / diverse beam search (group_size > 1, AttModel._diverse_sample) is not on the path')
+            raise NotImplementedError("diverse sampling / diverse beam search (group_size > 1, AttModel._diverse_sample) is not on the path: the "
+                                      "reference's own grouped search fails (CaptionModel.beam_search calls self.repeat_tensor, which no class defines)")
         if n < 1:
             raise ValueError('sample_n must be at least 1')
         method, param = parse_sample_method(args.get('sample_method', 'greedy'))
@@ -961,20 +1095,21 @@ def _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_ho
 
 
 @torch.no_grad()
-def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None):
+def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, return_logprobs=False):
     """beam_search without the persistent session (head dims other than 64, max_seq_len > 256, or the debugging switches): every call
-    allocates its state and captures its own graph."""
+    allocates its state and captures its own graph.  The options (beam_options) run through the same kernel as on the session path, which
+    needs the cache row table: without it (max_seq_len > 256, head dims other than 64) a search with options is refused."""
     was_training = dec.training
     dec.eval()
     try:
         beam, max_len = int(args.get('beam_size', 3)), int(args['max_seq_len'])
-        if args.get('group_size', 1) != 1 or args.get('sample_n', 1) != 1:
-            raise NotImplementedError('diverse beam search (group_size > 1) is not on the path')
+        opts = beam_options(args, beam, return_logprobs)
         if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
             raise ValueError('beam_size must be in [1, 8]')
         enc, src_mask = dec.encode(enc_states, enc_mask)
         B, dev = enc.shape[0], enc.device
         V1 = dec.vocab_size + 1
+        lists = _BeamLists(dec, B, beam, max_len, dev, opts) if opts is not None else None
         st = _DecoderState(dec, enc, src_mask, max_len)
         logp = st.step(torch.full((B,), dec.bos_idx, dtype=torch.long, device=dev))            # (B, V+1)
         base = torch.arange(B, device=dev).unsqueeze(1)
@@ -1019,19 +1154,28 @@ def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, st
             """book(None, last) as ONE launch (csrc/beam.hip): top-beam, sequence / cache-row-table / relational-memory reorder in
             place, finished-beam tracking, -1000 penalty, next input tokens -- and, between steps, the position counter's increment and
             the row-table column of the next position."""
-            lp = logp[0]
-            H.check(H.lib.evk_beam_step(H.ptr(lp), lp.shape[-1], V1, beam, B, max_len, H.ptr(pos), dec.eos_idx, int(last), H.ptr(beam_sum),
-                                        H.ptr(beam_seq), H.ptr(best_p), H.ptr(best_seq), H.ptr(words), H.ptr(st.mem32 if st.mem32 is not None else st.mem),
-                                        st.mem[0].numel() * (2 if st.mem32 is not None else 1), H.ptr(st.anc), st.anc.shape[1],
-                                        None if last else H.ptr(pos), H.ptr(ticket), None, H.stream()), 'beam_step')
+            _beam_step(dec, logp[0], beam, B, max_len, pos, last, beam_sum, beam_seq, best_p, best_seq, words,
+                       st.mem32 if st.mem32 is not None else st.mem, st.mem[0].numel() * (2 if st.mem32 is not None else 1), st.anc,
+                       None if last else pos, ticket, None, lists)
             return words
 
         nb = 1
         logp = [logp]
         hook = step_hook if step_hook is not None else (lambda *a: None)
         # t = 0 (the hypothesis count grows from B to B*beam here) runs eagerly
-        hook(0, logp[0], beam_sum)
-        w = book(0, max_len == 1)
+        if lists is not None:
+            lists.reset()
+            beam_sum.fill_(-float('inf'))
+            beam_sum[:, 0] = 0.0
+            hook(0, logp[0], beam_sum)
+            _beam_first_position(dec, logp[0], beam, B, max_len, beam_sum, beam_seq, best_p, best_seq, words, lists)
+            w = words.view(B, beam).clone()
+            if max_len > 1:
+                st.reorder(base.expand(B, beam).reshape(-1))           # every hypothesis starts from its study's state
+                st.logit_scale = 1.0 / opts['temperature']             # positions >= 1 only (att_model.py:119)
+        else:
+            hook(0, logp[0], beam_sum)
+            w = book(0, max_len == 1)
         if max_len > 1:
             nb = beam
             R = B * beam
@@ -1043,6 +1187,9 @@ def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, st
 
             fused_book = _FUSED_BOOK[0] and st.anc is not None and beam_seq.is_contiguous() and st.mem.is_contiguous()
             stats['fused_bookkeeping'] = bool(fused_book)
+            if lists is not None and not fused_book:
+                raise NotImplementedError('beam search options (temperature, decoding_constraint, length_penalty, sample_n, log-probabilities) '
+                                          'need the fused bookkeeping kernel and the cache row table (head dim 64, max_seq_len <= 256)')
 
             def body():
                 """steps 1 .. max_len-2: bookkeeping at position `pos`, then the decoder step that writes position pos+1."""
@@ -1122,6 +1269,8 @@ def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, st
                 book_kernel(True)                                        # t = max_len - 1: every live beam is closed
             else:
                 book(None, True)
+        if lists is not None:
+            return lists.result(return_scores)
         if return_scores:
             return best_seq, best_p
         return best_seq

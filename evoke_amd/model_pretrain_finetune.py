@@ -29,7 +29,8 @@ def decode_route(args):
     if args.get('beam_size', 1) > 1 and args.get('sample_method', 'greedy') in ('greedy', 'beam_search'):
         return 'beam'
     if args.get('group_size', 1) > 1:
-        raise NotImplementedError('diverse sampling (group_size > 1, AttModel._diverse_sample) is not on the path')
+        raise NotImplementedError("diverse sampling (group_size > 1, AttModel._diverse_sample) is not on the path: the reference's own grouped "
+                                  'search fails (CaptionModel.beam_search calls self.repeat_tensor, which no class defines)')
     return 'sample'
 
 

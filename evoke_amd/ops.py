@@ -1120,11 +1120,15 @@ def nll_loss(logits, target, wmask, V):
     return _NllLoss.apply(logits, target.contiguous(), wmask.contiguous(), V)
 
 
-def log_softmax(logits, V, out=None):
-    """f32 [rows, ld] -> f32 log-probs [rows, V] (decode path, no autograd)."""
+def log_softmax(logits, V, out=None, scale=1.0):
+    """f32 [rows, ld] -> f32 log-probs [rows, V] of logits * scale (decode path, no autograd).  scale = 1 / temperature of the beam search's
+    later positions; 1 takes the entry and the kernel it always took."""
     rows, ld = _rows(logits), logits.shape[-1]
     if out is None:
         out = _e(rows, V, dtype=F32, device=logits.device)
     assert out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (rows, V)
+    if scale != 1.0:
+        H.check(H.lib.evk_log_softmax_scaled(H.ptr(logits), H.ptr(out), rows, V, ld, V, C.c_float(scale), H.stream()), 'log_softmax_scaled')
+        return out
     H.check(H.lib.evk_log_softmax_nll_fwd(H.ptr(logits), H.ptr(out), None, None, None, None, rows, V, ld, V, H.stream()), 'log_softmax')
     return out

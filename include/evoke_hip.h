@@ -430,6 +430,11 @@ int evk_decode_attention_qkv(const void* qkv, int64_t ldq, void* k_cache, void* 
                              int32_t R, int32_t S, int32_t heads, int32_t head_dim, float scale, evk_stream_t stream);
 int evk_log_softmax_nll_fwd(const float* logits, float* logp, float* lse, const int64_t* target, const float* wmask, float* acc2,
                             int64_t rows, int32_t V, int32_t ld, int32_t ld_out, evk_stream_t stream);
+/* logp [rows][ld_out] = log_softmax(logits * scale) over the V valid columns: the temperature of the beam search's later steps,
+ * `F.log_softmax(logprobs / temperature)` (caption_model.py:196; for log-probability input the same as log_softmax(logits / temperature)),
+ * scale = 1 / temperature > 0.  A caller with scale 1 uses evk_log_softmax_nll_fwd: that entry and its kernel are unchanged.      */
+int evk_log_softmax_scaled(const float* logits, float* logp, int64_t rows, int32_t V, int32_t ld, int32_t ld_out, float scale,
+                           evk_stream_t stream);
 /* the masked-NLL forward with one value per row (row_nll[r] = -logp[r][target[r]] * wmask[r]) instead of the two atomically accumulated
  * sums: the caller adds the rows up (a tree reduction: the same bits on every run), lse as above.  loss.py:9-22 */
 int evk_log_softmax_nll_rows(const float* logits, float* lse, const int64_t* target, const float* wmask, float* row_nll, int64_t rows,
@@ -471,6 +476,29 @@ int evk_beam_step(const float* logp, int32_t ld, int32_t V1, int32_t beam, int32
                   int32_t force_end, float* beam_sum, int64_t* beam_seq, float* best_p, int64_t* best_seq, int64_t* words, void* mem,
                   int32_t mem_row, int32_t* anc, int32_t anc_cols, int64_t* pos_advance, int32_t* ticket, void* mem2, evk_stream_t stream);
 /* mem2 (optional): a second per-hypothesis state of mem_row 16-bit values re-ordered like mem (tanh of the relational memory) */
+/* evk_beam_step with the rest of CaptionModel.beam_search's working option set (group_size 1), same launch, same selection code:
+ *   decoding_constraint != 0 and *pos > 0: the column of each hypothesis's previous word counts as -inf while the rows are scanned
+ *     (caption_model.py:148-150); logp itself is not written.
+ *   finished list (caption_model.py:174-189, 199): every hypothesis that emits eos -- every live one under force_end -- enters its study's
+ *     list of `beam` entries with score = (double)running sum / len_div[*pos] (len_div [max_len] f64 = utils.penalty_builder's modifier
+ *     for length *pos + 1, computed by the caller; NULL = the running sum itself).  The list is kept sorted by score, descending, ties to
+ *     the earlier entry and within a step to the lower beam index (Python's stable sort), cut to `beam`: fin_score f64 [B][beam], fin_len
+ *     int32 [B][beam] (0 = empty slot; the caller zeroes it before position 0), fin_seq int64 [B][beam][max_len] padded with `pad`,
+ *     fin_anc int32 [B][beam][max_len] (optional): the row of logp that scored the entry's word at each position -- column *pos is the
+ *     parent's row, earlier columns are the parent's row of anc (the cache row table records exactly this; without anc they name the first
+ *     row of the study, which is exact at position 0 only).
+ *   hist f32 [max_len][B*beam][V1] (optional): slab *pos receives the V1 valid columns of every row as scanned (constraint applied) --
+ *     caption_model.py:84-99 keeps these rows per hypothesis and re-gathers them every step; evk_beam_gather_logprobs reads them once.
+ * With decoding_constraint 0, len_div NULL and hist NULL every array evk_beam_step writes receives the same bits. */
+int evk_beam_step_opts(const float* logp, int32_t ld, int32_t V1, int32_t beam, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                       int32_t force_end, float* beam_sum, int64_t* beam_seq, float* best_p, int64_t* best_seq, int64_t* words, void* mem,
+                       int32_t mem_row, int32_t* anc, int32_t anc_cols, int64_t* pos_advance, int32_t* ticket, void* mem2, int32_t pad,
+                       int32_t decoding_constraint, const double* len_div, double* fin_score, int32_t* fin_len, int64_t* fin_seq,
+                       int32_t* fin_anc, float* hist, evk_stream_t stream);
+/* seqLogprobs of the returned hypotheses (att_model.py:126-135): out f32 [B*take][max_len][V1], row b * take + k = entry k of study b's
+ * finished list (take = 1 or beam): out[row][t] = hist[t][fin_anc[b][k][t]] for t < fin_len[b][k], zeros beyond.  One launch after the search. */
+int evk_beam_gather_logprobs(const float* hist, const int32_t* fin_anc, const int32_t* fin_len, float* out, int32_t B, int32_t beam,
+                             int32_t take, int32_t max_len, int32_t V1, evk_stream_t stream);
 /* One launch for everything AttModel._sample does between two decoder steps (sample.hip; modules/att_model.py:176-221 and
  * CaptionModel.sample_next_word, modules/caption_model.py:363-401), for R independent rows.  logp [R][ld] f32 log-probs (V1 = V+1 valid
  * columns, V1 <= 4096); *pos = position t being written.  In the reference's order: decoding_constraint != 0 and t > 0: column seq[r][t-1]

@@ -1,0 +1,403 @@
+"""GPU tests of beam search with options: evk_beam_step_opts / evk_beam_gather_logprobs / evk_log_softmax_scaled through the C ABI against
+the CPU restatement (tests/beam_options_restatement.py, pinned to the reference by tests/test_beam_options_cpu.py), and
+evoke_amd.decode.beam_search at model level against the fixture the imported reference wrote (tests/golden/beam224_b4_opts.npz)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import beam_options_restatement as R
+from tests.golden.cases import CASES, make_inputs
+from tests.helpers import ARGS, STORE_DTYPE, V, load_procedural, load_tokenizer
+from tests.test_beam_options_cpu import MODEL, MODEL_BASE, MODEL_OPTS, decisive_studies, model_restatement
+from tests.test_hip_ops import close
+from tests.test_model_gpu import LOGP_TOL
+
+pytestmark = pytest.mark.gpu
+
+EOS, PAD = V - 1, 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- C ABI
+def synth_step(T, V1, eos, seed, start, eos_at_0):
+    """log-probabilities as a fixed function of position and last word without a (T, V1, V1) table: logits = A[t] + M[word % 17], the
+    [EOS] logit grows with the position (and leads at position 0 when eos_at_0)"""
+    g = torch.Generator().manual_seed(seed)
+    A, M = torch.randn(T, V1, generator=g) * 1.5, torch.randn(17, V1, generator=g) * 1.5
+    A[:, eos] += 0.8 * torch.arange(T, dtype=torch.float32) - 2.0
+    if eos_at_0:
+        A[0, eos] += 9.0
+    start = torch.as_tensor(start, dtype=torch.long)
+
+    def step(words, t, parent_rows):
+        w = start if words is None else words
+        return torch.log_softmax(A[t] + M[w % 17], -1)
+    return step
+
+
+class _Arrays:
+    """the device arrays of one search driven through the C ABI"""
+
+    def __init__(self, B, beam, T, V1, ld, mem_dtype, with_hist, len_div):
+        R_ = B * beam
+        dev = 'cuda'
+        self.B, self.beam, self.T, self.V1, self.ld = B, beam, T, V1, ld
+        self.lp = torch.full((R_, ld), 7.0, dtype=torch.float32, device=dev)              # pad columns hold a value that would win
+        self.pos = torch.zeros(1, dtype=torch.long, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.beam_sum = torch.full((B, beam), -float('inf'), device=dev)
+        self.beam_sum[:, 0] = 0.0
+        self.beam_seq = torch.zeros(B, beam, T, dtype=torch.long, device=dev)
+        self.best_p = torch.full((B,), -float('inf'), device=dev)
+        self.best_seq = torch.full((B, T), PAD, dtype=torch.long, device=dev)
+        self.words = torch.zeros(R_, dtype=torch.long, device=dev)
+        self.mem_row = 0
+        self.mem = None
+        if mem_dtype is not None:
+            # one recognisable row per hypothesis; mem_row counts 16-bit units (evk_beam_step's convention)
+            self.mem = (torch.arange(R_, device=dev).view(R_, 1) + torch.zeros(1, 96, device=dev)).to(mem_dtype).contiguous()
+            self.mem_row = 96 * (2 if mem_dtype == torch.float32 else 1)
+        self.anc = torch.arange(R_, dtype=torch.int32, device=dev).view(R_, 1).expand(R_, T).contiguous()
+        self.fin_score = torch.full((B, beam), -float('inf'), dtype=torch.float64, device=dev)
+        self.fin_len = torch.zeros(B, beam, dtype=torch.int32, device=dev)
+        self.fin_seq = torch.full((B, beam, T), PAD, dtype=torch.long, device=dev)
+        self.fin_anc = torch.zeros(B, beam, T, dtype=torch.int32, device=dev)
+        self.hist = torch.full((T, R_, V1), float('nan'), device=dev) if with_hist else None
+        self.len_div = torch.tensor(len_div, dtype=torch.float64, device=dev) if len_div is not None else None
+
+    def step(self, rows, last, eos, constraint, state, opts_entry=True):
+        """one call: rows (B * beam, V1) f32 log-probabilities of position *pos; state False = position 0 (no memory, no row table, no
+        advance); the position advances on the device otherwise"""
+        from evoke_amd import hip as H
+        self.lp[:, :self.V1] = rows.cuda()
+        adv = state and not last
+        head = (H.ptr(self.lp), self.ld, self.V1, self.beam, self.B, self.T, H.ptr(self.pos), eos, int(last), H.ptr(self.beam_sum),
+                H.ptr(self.beam_seq), H.ptr(self.best_p), H.ptr(self.best_seq), H.ptr(self.words), H.ptr(self.mem) if state else None,
+                self.mem_row if state else 0, H.ptr(self.anc) if state else None, self.T if state else 0, H.ptr(self.pos) if adv else None,
+                H.ptr(self.ticket) if adv else None, None)
+        if opts_entry:
+            H.check(H.lib.evk_beam_step_opts(*head, PAD, int(constraint), H.ptr(self.len_div), H.ptr(self.fin_score), H.ptr(self.fin_len),
+                                             H.ptr(self.fin_seq), H.ptr(self.fin_anc), H.ptr(self.hist), H.stream()), 'beam_step_opts')
+        else:
+            H.check(H.lib.evk_beam_step(*head, H.stream()), 'beam_step')
+        if not adv and not last:
+            self.pos += 1                   # position 0 -> 1 by hand; the row table's column 1 already names every row itself
+        return self.words.cpu()
+
+
+GEOMS = [  # beam, B, V1, ld, max_len, eos at position 0, memory rows
+    (1, 3, 23, 23, 12, False, None), (2, 2, 37, 40, 12, False, torch.float32), (3, 3, 23, 29, 24, False, STORE_DTYPE),
+    (4, 2, 1445, 1448, 16, False, torch.float32), (5, 2, 61, 64, 10, True, None), (6, 1, 101, 101, 9, False, STORE_DTYPE),
+    (7, 2, 37, 37, 8, True, torch.float32), (8, 2, 1445, 1448, 12, False, torch.float32), (4, 2, 1700, 1704, 10, False, STORE_DTYPE),
+    (3, 2, 1999, 1999, 6, True, None), (4, 3, 23, 24, 1, False, None), (4, 3, 23, 24, 2, False, torch.float32), (3, 2, 37, 37, 1, True, None),
+    (3, 2, 37, 37, 2, True, torch.float32),
+]
+OPTION_SETS = {'nbest': {}, 'all': dict(length_penalty='wu_0.9', temperature=2.0, decoding_constraint=1), 'avg': dict(length_penalty='avg_0')}
+
+
+@pytest.mark.parametrize('oname', list(OPTION_SETS))
+@pytest.mark.parametrize('geom', GEOMS, ids=lambda g: 'k%d_B%d_V%d_ld%d_L%d%s_%s' % (g[0], g[1], g[2], g[3], g[4], '_eos0' if g[5] else '',
+                                                                                        {None: 'nomem', torch.float32: 'f32'}.get(g[6], 'm16')))
+def test_beam_options_step_and_gather_kernels_equal_the_restatement(geom, oname):
+    """evk_beam_step_opts position by position and evk_beam_gather_logprobs at the end, on the same f32 log-probabilities the restatement
+    sees (the rows of position t + 1 are built on the host from the kernel's `words`): next words, live hypotheses, running sums, list ids,
+    lengths, row ancestry, the gathered log-probability rows and the re-ordered memory rows bit for bit; list scores to the last f32 bit
+    of the running sum.  V1 <= 1536 takes the register kernel, larger ones the scanning kernel."""
+    from evoke_amd import hip as H
+    beam, B, V1, ld, T, eos0, mem_dtype = geom
+    opts = OPTION_SETS[oname]
+    eos = V1 - 2
+    temperature = float(opts.get('temperature', 1.0))
+    start = [(3 + 5 * b) % (V1 - 2) for b in range(B)]
+    raw_step = synth_step(T, V1, eos, 7 * beam + T, start, eos0)
+    calls = []
+
+    def rec_step(words, t, parent_rows):
+        out = raw_step(words, t, parent_rows)
+        calls.append((None if words is None else words.clone(), out))
+        return out
+
+    want = R.beam_search(rec_step, B, beam, T, eos, opts)
+    a = _Arrays(B, beam, T, V1, ld, mem_dtype, True, R.length_divisors(opts.get('length_penalty', ''), T))
+    constraint = opts.get('decoding_constraint', 0)
+    rows = calls[0][1].repeat_interleave(beam, 0)
+    for t in range(T):
+        words = a.step(rows, t == T - 1, eos, constraint, state=t > 0)
+        assert words.tolist() == (want['trace'][t]['flat'][:, :beam] % V1).reshape(-1).tolist(), 'words of position %d' % t
+        if t + 1 < T:
+            assert torch.equal(words, calls[t + 1][0])
+            rows = F.log_softmax(raw_step(words, t + 1, None).float() / temperature, dim=-1)
+    torch.cuda.synchronize()
+    assert int(a.ticket.item()) == 0 and int(a.pos.item()) == T - 1
+    assert torch.equal(a.beam_seq.cpu(), want['live_seq']) and torch.equal(a.beam_sum.cpu(), want['live_sum'])
+    seq, slp, scores, lens = R.output(want, B, beam, T, beam, PAD)
+    assert torch.equal(a.fin_seq.cpu().view(B * beam, T), seq)
+    assert a.fin_len.cpu().view(-1).tolist() == lens.tolist()
+    got_scores = a.fin_score.cpu().view(-1).numpy()
+    print('\n[%s] list lengths %s; largest |score - restatement| %.3g' % (oname, sorted(set(lens.tolist())), np.abs(got_scores - scores).max()))
+    np.testing.assert_allclose(got_scores, scores, rtol=2.0 ** -24, atol=0)
+    anc = a.fin_anc.cpu().view(B * beam, T)
+    for r in range(B * beam):
+        e = want['done'][r // beam][r % beam]
+        assert anc[r, 1:e['len']].tolist() == e['rows'][1:].tolist(), r           # (column 0: any row of the study holds the same slab)
+        assert r // beam * beam <= int(anc[r, 0]) < (r // beam + 1) * beam
+    for take in (1, beam):
+        out = torch.full((B * take, T, V1), float('nan'), device='cuda')
+        H.check(H.lib.evk_beam_gather_logprobs(H.ptr(a.hist), H.ptr(a.fin_anc), H.ptr(a.fin_len), H.ptr(out), B, beam, take, T, V1, H.stream()),
+                'beam_gather_logprobs')
+        assert torch.equal(out.cpu(), R.output(want, B, beam, T, take, PAD)[1]), 'gathered rows, take %d' % take
+    if mem_dtype is not None and T > 1:
+        assert a.mem.float().cpu()[:, 0].long().tolist() == want['live_rows'][:, :, 1].reshape(-1).tolist()
+        assert bool((a.mem == a.mem[:, :1]).all())
+
+
+@pytest.mark.parametrize('geom', [GEOMS[2], GEOMS[3], GEOMS[8], GEOMS[6]], ids=['k3_V23', 'k4_V1445', 'k4_V1700', 'k7_eos0'])
+def test_beam_options_entry_with_every_option_off_leaves_what_evk_beam_step_leaves(geom):
+    beam, B, V1, ld, T, eos0, mem_dtype = geom
+    eos = V1 - 2
+    raw_step = synth_step(T, V1, eos, 11, [(3 + 5 * b) % (V1 - 2) for b in range(B)], eos0)
+    new, old = (_Arrays(B, beam, T, V1, ld, mem_dtype, False, None) for _ in range(2))
+    rows = raw_step(None, 0, None).repeat_interleave(beam, 0)
+    for t in range(T):
+        w_new = new.step(rows, t == T - 1, eos, 0, state=t > 0)
+        w_old = old.step(rows, t == T - 1, eos, 0, state=t > 0, opts_entry=False)
+        assert torch.equal(w_new, w_old)
+        for name in ('beam_sum', 'beam_seq', 'best_p', 'best_seq', 'anc', 'mem', 'pos'):
+            x, y = getattr(new, name), getattr(old, name)
+            assert x is None and y is None or torch.equal(x, y), (name, t)
+        if t + 1 < T:
+            rows = raw_step(w_new, t + 1, None)
+    # ... and the list's first entry is the hypothesis evk_beam_step tracks as the best finished one
+    assert torch.equal(new.fin_seq[:, 0], new.best_seq) and torch.equal(new.fin_score[:, 0].float(), new.best_p)
+
+
+def test_beam_options_entries_refuse_bad_arguments():
+    from evoke_amd import hip as H
+    a = _Arrays(2, 3, 4, 23, 24, None, True, None)
+    head = lambda **k: (H.ptr(a.lp), k.get('ld', 24), 23, k.get('beam', 3), 2, 4, H.ptr(a.pos), 21, 0, H.ptr(a.beam_sum), H.ptr(a.beam_seq),       # noqa: E731
+                        H.ptr(a.best_p), H.ptr(a.best_seq), H.ptr(a.words), None, 0, None, 0, None, None, None)
+    tail = lambda **k: (PAD, 0, None, k.get('score', H.ptr(a.fin_score)), H.ptr(a.fin_len), H.ptr(a.fin_seq), H.ptr(a.fin_anc), None, H.stream())   # noqa: E731
+    assert H.lib.evk_beam_step_opts(*head(), *tail(score=None)) == -1 and b'finished list' in H.lib.evk_last_error()
+    assert H.lib.evk_beam_step_opts(*head(beam=9), *tail()) == -1
+    assert H.lib.evk_beam_step_opts(*head(ld=22), *tail()) == -1
+    out = torch.zeros(2 * 3, 4, 23, device='cuda')
+    g = lambda **k: H.lib.evk_beam_gather_logprobs(k.get('hist', H.ptr(a.hist)), H.ptr(a.fin_anc), H.ptr(a.fin_len), H.ptr(out), 2, 3,            # noqa: E731
+                                                   k.get('take', 3), 4, 23, H.stream())
+    assert g(hist=None) == -1 and g(take=4) == -1 and g(take=0) == -1
+    assert H.lib.evk_log_softmax_scaled(H.ptr(a.lp), H.ptr(a.lp), 6, 23, 24, 24, C.c_float(0.0), H.stream()) == -1
+    assert H.lib.evk_log_softmax_scaled(None, H.ptr(a.lp), 6, 23, 24, 24, C.c_float(1.0), H.stream()) == -1
+
+
+@pytest.mark.parametrize('Vn,ld', [(1445, 1448), (5000, 5000), (37, 40)])
+def test_scaled_log_softmax_against_float64(Vn, ld):
+    """evk_log_softmax_scaled vs torch in float64 on the same f32 logits, to the bound the unscaled kernel is held to
+    (tests/test_hip_ops.py: 1e-5 + 1e-5 |x|); a scale of 1 gives the unscaled entry's bits"""
+    from evoke_amd import hip as H, ops
+    rows = 300
+    lg = torch.zeros(rows, ld)
+    lg[:, :Vn] = torch.randn(rows, Vn, generator=torch.Generator().manual_seed(5))
+    lgd = lg.cuda()
+    plain = ops.log_softmax(lgd, Vn)
+    one = torch.empty_like(plain)
+    H.check(H.lib.evk_log_softmax_scaled(H.ptr(lgd), H.ptr(one), rows, Vn, ld, Vn, C.c_float(1.0), H.stream()), 'log_softmax_scaled')
+    assert torch.equal(one, plain) and torch.equal(ops.log_softmax(lgd, Vn, scale=1.0), plain)
+    close(plain, F.log_softmax(lg[:, :Vn].double(), -1).float(), 1e-5, 1e-5, 'log_softmax')
+    for scale in (1.0 / 3.0, 2.0, 0.5):
+        s32 = float(np.float32(scale))
+        want = F.log_softmax(lg[:, :Vn].double() * s32, -1)
+        got = ops.log_softmax(lgd, Vn, scale=scale)
+        err = (got.cpu().double() - want).abs()
+        print('\n[V %d scale %.3f] max |err| %.3g' % (Vn, scale, err.max().item()))
+        assert bool((err <= 1e-5 + 1e-5 * want.abs()).all()), err.max().item()
+
+
+# ---------------------------------------------------------------------------------------------------------------- model level
+def _args(oname, **kw):
+    case = CASES[MODEL_BASE]
+    return dict(ARGS, max_seq_len=case['max_seq_len'], beam_size=case['beam_size'], **dict(MODEL_OPTS[oname], **kw))
+
+
+@pytest.fixture(scope='module')
+def model():
+    from evoke_amd.model_pretrain_finetune import FineTune
+    from oracle import spec as S
+    m = FineTune(_args('nbest'), load_tokenizer(), 'iu_xray')
+    load_procedural(m, S.finetune_spec(V))
+    m.eval()
+    return m
+
+
+@pytest.fixture(scope='module')
+def enc(model):
+    case = CASES[MODEL_BASE]
+    inp = make_inputs(case, V)
+    with torch.no_grad():
+        return model.encoder_states(inp['images'].cuda(), np.array(inp['patient_ids']), case['B'], inp['inc_ids'], inp['inc_masks'])
+
+
+def _first_open(res, tol):
+    """per study, the first position whose selection margin in the restatement is below 2 x tol (max_len when none is)"""
+    m = res['margin']
+    return [int(np.argmax(m[:, b] < 2 * tol)) if (m[:, b] < 2 * tol).any() else m.shape[0] for b in range(m.shape[1])]
+
+
+@pytest.mark.parametrize('oname', list(MODEL_OPTS))
+def test_beam_options_end_to_end_on_the_reference_fixture(model, enc, oname):
+    """decode.beam_search on case beam224_b4 under each option set of tests/golden/beam224_b4_opts.npz (written by the reference FineTune).
+
+    The rule of test_beam_search_matches_reference -- ids identical for every study whose selections and list ranks all had a margin of
+    >= 2 x LOGP_TOL in the restatement's trace -- is applied as stated, but on this untrained network it admits NO study under any of the
+    four option sets (smallest selection margin per study: n-best 5.0e-4 / 3.0e-3, temperature 3 3.3e-4 / 1.4e-4, constraint 5.0e-4 /
+    2.0e-3, all with wu_0.9 3.3e-4 / 1.4e-4; tests/test_beam_options_cpu.py prints them), so it cannot carry the test.  The search is
+    therefore pinned the way test_beam_search_follows_the_reference_decisions pins it:
+      1. TEACHER-FORCED along the restatement's trace (which equals the reference's ids, scores and log-probabilities on the CPU): at every
+         position the engine's log-probabilities of the traced candidates (after temperature) agree to LOGP_TOL, and the forced search
+         returns the reference's rows exactly -- all beam_size list entries under sample_n = beam_size --, its list scores and lengths.
+      2. FREE-RUNNING with log-probabilities: decisive studies (none here) must return the reference's ids; every study's best row agrees
+         with the reference up to the first position whose margin is below 2 x LOGP_TOL, with the chosen words' log-probabilities
+         within LOGP_TOL there; the returned rows are consistent with the returned list: the chosen words' log-probabilities add up to
+         the list score times the length modifier, rows are zero beyond the length, and the constraint's column is -inf."""
+    from evoke_amd import decode
+    case, opts, args = CASES[MODEL_BASE], MODEL_OPTS[oname], _args(oname)
+    B, beam, T, V1 = case['B'], case['beam_size'], case['max_seq_len'], V + 1
+    n = opts.get('sample_n', 1)
+    res = model_restatement(oname)
+    x, enc_mask = enc
+    flat = torch.stack([tr['flat'] for tr in res['trace']]).cuda()               # (T, B, K)
+    score = torch.stack([tr['score'] for tr in res['trace']]).cuda()
+    ref_lp = torch.stack([tr['logp'] for tr in res['trace']]).cuda()
+    err = []
+
+    def forced(t, logp, beam_sum):
+        nb = 1 if t == 0 else beam
+        parent, word = flat[t] // V1, flat[t] % V1
+        rows = parent + torch.arange(B, device='cuda').unsqueeze(1) * nb
+        got = logp[rows, word]
+        fin = torch.isfinite(ref_lp[t])
+        err.append(torch.where(fin, got - ref_lp[t], torch.zeros_like(got)).abs().max().item())
+        new = torch.full_like(logp, -1e30)
+        new[rows[:, :beam], word[:, :beam]] = score[t][:, :beam] - beam_sum[:, :nb].gather(1, parent[:, :beam])
+        logp.copy_(new)
+
+    seq_f, p_f = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, step_hook=forced)
+    assert decode.stats.get('graph') and decode.stats.get('replayer'), decode.stats
+    print('\n[%s] teacher-forced |logp - reference| over the traced candidates: max %.2e (tolerance %.1e)' % (oname, max(err), LOGP_TOL))
+    assert len(err) == T and max(err) <= LOGP_TOL
+    assert torch.equal(seq_f.cpu(), torch.from_numpy(MODEL[oname + '/seq'])), 'the forced search does not return the reference rows'
+    np.testing.assert_allclose(p_f.cpu().numpy().reshape(B, n), MODEL[oname + '/scores'][:, :n], atol=2e-3, rtol=0)
+    # ---- free-running
+    seq, slp, p = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
+    seq, slp, p = seq.cpu(), slp.cpu(), p.cpu().numpy()
+    assert tuple(seq.shape) == (B * n, T) and tuple(slp.shape) == (B * n, T, V1) and p.dtype == np.float64
+    want = torch.from_numpy(MODEL[oname + '/seq'])
+    dec = decisive_studies(res, n, LOGP_TOL)
+    first = _first_open(res, LOGP_TOL)
+    print('   free-running: decisive studies %s; best row identical to the reference for %s positions (first open position %s)' % (
+        dec.tolist(), [int((seq[b * n] == want[b * n]).long().cumprod(0).sum()) for b in range(B)], first))
+    chosen = slp.gather(2, seq.unsqueeze(-1))[..., 0]
+    for b in range(B):
+        if dec[b]:
+            assert torch.equal(seq[b * n:(b + 1) * n], want[b * n:(b + 1) * n]), b
+        q = first[b]
+        assert seq[b * n, :q].tolist() == want[b * n, :q].tolist(), (b, q)
+        assert (chosen[b * n, :q] - torch.from_numpy(MODEL[oname + '/chosen'][b * n, :q])).abs().max().item() <= LOGP_TOL
+    div = R.length_divisors(opts.get('length_penalty', ''), T)
+    assert (MODEL[oname + '/lens'] == T).all()                                   # (an untrained network never emits [EOS]: every row runs to the end)
+    np.testing.assert_allclose(chosen.double().sum(1).numpy(), p * (div[T - 1] if div is not None else 1.0), atol=1e-3, rtol=0)
+    assert (p.reshape(B, n)[:, :-1] >= p.reshape(B, n)[:, 1:]).all()
+    if opts.get('decoding_constraint'):
+        assert torch.isneginf(slp[:, 1:].gather(2, seq[:, :-1].unsqueeze(-1))).all()
+        assert torch.isfinite(slp[:, 0]).all()
+    else:
+        assert torch.isfinite(slp).all()
+    assert (torch.logsumexp(slp, -1).abs() <= 1e-3).all() or opts.get('decoding_constraint')
+    decode._SESSIONS.clear()
+
+
+@pytest.mark.parametrize('oname', list(MODEL_OPTS) + ['avg_nbest'])
+def test_beam_options_session_path_equals_the_legacy_path(model, enc, oname):
+    from evoke_amd import decode
+    args = _args(oname) if oname in MODEL_OPTS else _args('nbest', length_penalty='avg_0')
+    x, enc_mask = enc
+    seq, slp, p = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
+    assert decode.stats.get('graph')
+    saved = decode._GRAPH_ENABLED[0]
+    decode._GRAPH_ENABLED[0] = False                                              # no session: _beam_search_legacy, eager steps
+    try:
+        seq_l, slp_l, p_l = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
+    finally:
+        decode._GRAPH_ENABLED[0] = saved
+    assert not decode.stats.get('graph')
+    assert torch.equal(seq, seq_l) and torch.equal(p, p_l) and torch.equal(slp, slp_l)
+    seq_only = decode.beam_search(model.text_decoder, x, enc_mask, args)
+    assert torch.equal(seq_only, seq)
+    decode._SESSIONS.clear()
+
+
+def test_beam_options_do_not_share_a_session_and_defaults_keep_their_launches(model, enc):
+    """two option sets one after the other on the same decoder; the plain search keeps its session key, its results and the launch count
+    of its captured step; the option sets add none to the step"""
+    from evoke_amd import decode
+    x, enc_mask = enc
+    dec = model.text_decoder
+    decode._SESSIONS.clear()
+    plain_args = dict(_args('nbest'), sample_n=1)
+    plain, plain_p = decode.beam_search(dec, x, enc_mask, plain_args, return_scores=True)
+    launches = decode.stats['step_launches']
+    assert len(decode._SESSIONS[dec]) == 1 and all(len(k) == 7 for k in decode._SESSIONS[dec])
+    a1 = decode.beam_search(dec, x, enc_mask, _args('constraint'))
+    assert decode.stats['step_launches'] == launches
+    a2 = decode.beam_search(dec, x, enc_mask, _args('temp_3'))
+    assert decode.stats['step_launches'] == launches
+    assert len(decode._SESSIONS[dec]) == 3
+    b1 = decode.beam_search(dec, x, enc_mask, _args('constraint'))
+    nb, nb_lp, nb_p = decode.beam_search(dec, x, enc_mask, _args('nbest'), return_scores=True, return_logprobs=True)
+    assert decode.stats['step_launches'] == launches
+    again = decode.beam_search(dec, x, enc_mask, plain_args)
+    assert torch.equal(a1, b1) and not torch.equal(a1, a2) and not torch.equal(a1, plain)
+    assert torch.equal(again, plain) and torch.equal(nb[::4], plain)
+    assert torch.equal(nb_p[::4].float(), plain_p)                                # the list's first score is today's best_p
+    assert plain_p.dtype == torch.float32 and tuple(nb.shape) == (8, plain.shape[1])
+    decode._SESSIONS.clear()
+
+
+@pytest.mark.parametrize('env', [{}, {'EVK_DECODE_THREADS': '1', 'EVK_DECODE_DEPTH': '2', 'EVK_DECODE_BURST': '5'}], ids=['one_thread', 'threads_burst5'])
+def test_beam_options_pipelined_generation_returns_the_per_batch_rows(env, monkeypatch):
+    """FineTune(mode='inference') with sample_n = beam_size and the other options: B * beam_size rows and as many texts (the no-finding text
+    applies per row), and generate_pipelined returns what the per-batch call returns in both driving modes"""
+    from evoke_amd import decode
+    from evoke_amd.model_pretrain_finetune import NO_FINDING, FineTune
+    from oracle import spec as S
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    case = CASES[MODEL_BASE]
+    m = FineTune(_args('all_wu'), load_tokenizer(), 'iu_xray')
+    load_procedural(m, S.finetune_spec(V))
+    m.eval()
+    inp = make_inputs(case, V)
+    batch = (inp['images'].cuda(), inp['ids'].cuda(), inp['masks'].cuda(), np.array(inp['patient_ids']), inp['inc_ids'], inp['inc_masks'])
+    with torch.no_grad():
+        texts, seq = m(*batch, mode='inference')
+        piped = list(m.generate_pipelined([batch, batch, batch], mode='inference'))
+    rows = case['B'] * case['beam_size']
+    assert tuple(seq.shape) == (rows, case['max_seq_len']) and len(texts) == rows and all(len(t) > 0 for t in texts)
+    assert texts == [t if t else NO_FINDING for t in load_tokenizer().decode_batch(seq.cpu().tolist())]
+    assert len(piped) == 3
+    for pt, ps in piped:
+        assert pt == texts and torch.equal(ps.cpu(), seq.cpu())
+    decode._SESSIONS.clear()
+
+
+def test_beam_options_validation_on_the_device_routes(model, enc):
+    from evoke_amd import decode
+    x, enc_mask = enc
+    dec = model.text_decoder
+    for bad, exc, pat in ((dict(length_penalty='harmonic_2'), ValueError, 'length_penalty'), (dict(sample_n=3), ValueError, 'sample_n'),
+                          (dict(temperature=0.0), ValueError, 'temperature'), (dict(group_size=2), NotImplementedError, 'repeat_tensor')):
+        with pytest.raises(exc, match=pat):
+            decode.beam_search(dec, x, enc_mask, _args('nbest', **bad))
+    with pytest.raises(NotImplementedError, match='repeat_tensor'):
+        decode.sample(dec, x, enc_mask, dict(_args('nbest'), beam_size=1, sample_n=1, group_size=2))
+    assert not dec.training
