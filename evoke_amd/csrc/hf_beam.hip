@@ -1,0 +1,207 @@
+// hf_beam.hip -- one kernel per generated token for ALL the beam bookkeeping of the distilgpt2 backend's search: what Hugging Face's
+// classic BeamSearchScorer does between two decoder steps at length_penalty 1, early_stopping False (language_model.py:271-280 hands the
+// search to `generate`; oracle/gpt2.py:120-186 restates it).  The first engine did this on the host: two device -> host copies per
+// token, a Python double loop over studies x 2 * num_beams candidates, index_select over every self-attention cache.  Here: one
+// workgroup per study --
+//   1. candidate = running score of the source beam + log-probability (f32 add); every thread keeps the top 2 * nb of its strided share
+//      of the nb x V candidates, 2 * nb rounds of a block arg-max pick them in descending order (ties -> lowest flat index);
+//   2. thread 0 walks the ranks: an [EOS] candidate at rank < nb enters the study's sorted hypothesis list with score sum / cur_len (f64),
+//      an [EOS] candidate at rank >= nb is skipped, the first nb other candidates are the next beams; then the done flag;
+//   3. the study's sequences and cache row tables are staged in LDS and rewritten IN PLACE in the winners' order, the new token goes to
+//      column *pos + 1, the row table's next column is seeded, and the last workgroup to finish advances the position.
+// A study that is done emits [PAD] from its first row for ever and never touches its list again, so steps issued after every study is
+// done change nothing that is returned.
+#include <stdlib.h>
+#include "common.h"
+
+namespace {
+
+constexpr int NBMAX = 8;
+
+struct HfBeamP {
+  const float* logp; int ld;           // [B*nb][ld] f32 log-probs of the step, V valid columns
+  int V, nb, max_len, eos, pad, force_end;
+  const long long* pos;                // device scalar: last filled column of seqs (cur_len = *pos + 1 generated tokens after this step)
+  float* scores;                       // [B][nb] running sums (in / out)
+  long long* seqs;                     // [B*nb][max_len] (in place), column 0 = [BOS]
+  long long* words;                    // [B*nb] out: tokens fed to the next decoder step
+  int* anc; int anc_cols;              // cache row table [B*nb][anc_cols] (in place) or null
+  double* hyp_score; int* hyp_len;     // [B][nb] sorted hypothesis list: score descending (ties: earlier entry first), columns (0 = empty)
+  long long* hyp_seq;                  // [B][nb][max_len] with the leading [BOS], padded with `pad`
+  unsigned char* done; int* n_done;    // [B] flags (in / out); *n_done += studies that became done in this launch
+  long long* pos_out; int* ticket;     // the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
+};
+
+template <int K2>                      // capacity of a thread's candidate list: >= 2 * nb
+__global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ float s_val[4]; __shared__ int s_idx[4];
+  __shared__ float win_v[2 * NBMAX]; __shared__ int win_i[2 * NBMAX];
+  __shared__ float nx_sc[NBMAX]; __shared__ int nx_tok[NBMAX]; __shared__ int nx_src[NBMAX];
+  __shared__ double f_sc[NBMAX]; __shared__ int f_ln[NBMAX]; __shared__ int f_src[NBMAX];
+  __shared__ int s_list;               // the list's rows move in this launch
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = p.nb, V = p.V, k2 = 2 * nb;
+  const long pos = p.pos[0];
+  const bool was_done = p.done[b] != 0;                       // (block-uniform)
+  // ---- 0. the study's rows -> LDS
+  long long* seq = p.seqs + (long)b * nb * p.max_len;
+  long long* l_seq = reinterpret_cast<long long*>(smem);                               // [nb][max_len]
+  int* l_anc = reinterpret_cast<int*>(l_seq + (size_t)nb * p.max_len);                 // [nb][anc_cols]
+  for (int i = tid; i < nb * p.max_len; i += 256) l_seq[i] = seq[i];
+  if (p.anc) for (int i = tid; i < nb * p.anc_cols; i += 256) l_anc[i] = p.anc[(long)b * nb * p.anc_cols + i];
+  if (!was_done) {
+    // ---- 1. the 2 * nb best candidates, descending
+    float bv[K2]; int bi[K2];
+#pragma unroll
+    for (int j = 0; j < K2; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
+    constexpr int UNR = 8;             // a thread's share of one source beam is requested in one batch, then inserted (see beam.hip)
+    for (int src = 0; src < nb; ++src) {
+      const float base = p.scores[b * nb + src];
+      const float* row = p.logp + (long)(b * nb + src) * p.ld;
+      for (int w0 = tid; w0 < V; w0 += 256 * UNR) {
+        float lv[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) { const int w = w0 + 256 * u; lv[u] = w < V ? row[w] : 0.f; }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          const int w = w0 + 256 * u;
+          if (w >= V) continue;
+          float v = base + lv[u];
+          int id = src * V + w;
+          if (!(v > bv[K2 - 1] || (v == bv[K2 - 1] && id < bi[K2 - 1])) && k2 == K2) continue;     // (cannot enter a full-depth list)
+#pragma unroll
+          for (int j = 0; j < K2; ++j)
+            if (j < k2 && (v > bv[j] || (v == bv[j] && id < bi[j]))) { const float tv = bv[j]; const int ti = bi[j]; bv[j] = v; bi[j] = id; v = tv; id = ti; }
+        }
+      }
+    }
+    for (int r = 0; r < k2; ++r) {
+      float best = bv[0]; int bid = bi[0];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bid, o, 64);
+        if (ov > best || (ov == best && oi < bid)) { best = ov; bid = oi; }
+      }
+      if (lane == 0) { s_val[wave] = best; s_idx[wave] = bid; }
+      __syncthreads();
+      if (tid == 0) {
+        float fv = s_val[0]; int fi = s_idx[0];
+        for (int w = 1; w < 4; ++w) if (s_val[w] > fv || (s_val[w] == fv && s_idx[w] < fi)) { fv = s_val[w]; fi = s_idx[w]; }
+        // no comparable candidate left (every remaining log-probability NaN): rank r takes flat index r (source beam 0, token r < V) at
+        // -inf, a defined in-range state instead of a sentinel that would address rows beyond the study's beams below
+        if (fi == 0x7fffffff) { fv = -INFINITY; fi = r; }
+        win_v[r] = fv; win_i[r] = fi;
+      }
+      __syncthreads();
+      if (bi[0] == win_i[r]) {          // the owner pops its head
+#pragma unroll
+        for (int j = 0; j + 1 < K2; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
+        bv[K2 - 1] = -INFINITY; bi[K2 - 1] = 0x7fffffff;
+      }
+    }
+  }
+  // ---- 2. the rank walk (thread 0): hypothesis list, next beams, done flag
+  if (tid == 0) {
+    int moved = 0;
+    if (was_done) {
+      for (int k = 0; k < nb; ++k) { nx_sc[k] = 0.f; nx_tok[k] = p.pad; nx_src[k] = 0; }
+    } else {
+      const double cur_len = (double)(pos + 1);
+      int nx_rank[NBMAX];
+      for (int k = 0; k < nb; ++k) { f_sc[k] = p.hyp_score[b * nb + k]; f_ln[k] = p.hyp_len[b * nb + k]; f_src[k] = k; }
+      // an entry enters below every entry that is at least as good (Python's stable sort of the appended list), the list is cut to nb;
+      // f_src remembers where a slot's row comes from: an old slot (< nb) or the candidate of rank f_src - nb
+      auto insert = [&](double s, int rank) {
+        int k = 0;
+        while (k < nb && f_ln[k] != 0 && !(s > f_sc[k])) ++k;
+        if (k >= nb) return;
+        for (int q = nb - 1; q > k; --q) { f_sc[q] = f_sc[q - 1]; f_ln[q] = f_ln[q - 1]; f_src[q] = f_src[q - 1]; }
+        f_sc[k] = s; f_ln[k] = (int)pos + 2; f_src[k] = nb + rank;
+        moved = 1;
+      };
+      int k = 0;
+      for (int rank = 0; rank < k2 && k < nb; ++rank) {
+        const int src = win_i[rank] / V, tok = win_i[rank] - src * V;
+        if (tok == p.eos) {
+          if (rank < nb) insert((double)win_v[rank] / cur_len, rank);
+          continue;
+        }
+        nx_sc[k] = win_v[rank]; nx_tok[k] = tok; nx_src[k] = src; nx_rank[k] = rank;
+        ++k;
+      }
+      for (; k < nb; ++k) { nx_sc[k] = -INFINITY; nx_tok[k] = p.pad; nx_src[k] = 0; nx_rank[k] = 0; }     // (V >= 2 * nb: never taken on finite rows)
+      const bool now_done = f_ln[nb - 1] != 0 && f_sc[nb - 1] >= (double)win_v[0] / cur_len;
+      if (now_done) { p.done[b] = 1; atomicAdd(p.n_done, 1); }
+      else if (p.force_end)
+        for (int j = 0; j < nb; ++j) insert((double)nx_sc[j] / cur_len, nx_rank[j]);
+      if (moved) for (int j = 0; j < nb; ++j) { p.hyp_score[b * nb + j] = f_sc[j]; p.hyp_len[b * nb + j] = f_ln[j]; }
+    }
+    s_list = moved;
+  }
+  __syncthreads();
+  // ---- 3. the list's rows: entries only move DOWN, so walking the slots from the bottom up lets a thread read a column before it
+  // overwrites it (as finished_list_insert of beam.hip)
+  if (s_list)
+    for (int c = tid; c < p.max_len; c += 256)
+      for (int d = nb - 1; d >= 0; --d) {
+        const int s = f_src[d];
+        if (s == d) continue;
+        long long w;
+        if (s < nb) w = p.hyp_seq[(long)(b * nb + s) * p.max_len + c];
+        else {
+          const int src = win_i[s - nb] / V;
+          w = c <= pos ? l_seq[src * p.max_len + c] : c == pos + 1 ? (long long)(win_i[s - nb] - src * V) : (long long)p.pad;
+        }
+        p.hyp_seq[(long)(b * nb + d) * p.max_len + c] = w;
+      }
+  // ---- 4. the study's rows in the winners' order, the new token in column pos + 1
+  for (int i = tid; i < nb * p.max_len; i += 256) {
+    const int j = i / p.max_len, c = i - j * p.max_len;
+    seq[i] = c == pos + 1 ? (long long)nx_tok[j] : l_seq[nx_src[j] * p.max_len + c];
+  }
+  if (p.anc)
+    for (int i = tid; i < nb * p.anc_cols; i += 256) {
+      const int j = i / p.anc_cols, c = i - j * p.anc_cols;
+      // the next decoder step writes its keys / values at position pos + 1 of every hypothesis's OWN cache row
+      p.anc[(long)b * nb * p.anc_cols + i] = c == pos + 1 ? b * nb + j : l_anc[nx_src[j] * p.anc_cols + c];
+    }
+  if (tid < nb) { p.scores[b * nb + tid] = nx_sc[tid]; p.words[b * nb + tid] = nx_tok[tid]; }
+  if (p.pos_out) {
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence();
+      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                     int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
+                     double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
+                     int32_t* ticket, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(nb >= 1 && nb <= NBMAX, "hf_beam_step: nb must be in [1, %d] (got %d)", NBMAX, nb);
+  EVK_REQUIRE(V >= 2 * nb && (int64_t)nb * V < INT32_MAX, "hf_beam_step: V=%d must hold 2 * nb = %d candidates", V, 2 * nb);
+  EVK_REQUIRE(ld >= V, "hf_beam_step: ld=%d < V=%d", ld, V);
+  EVK_REQUIRE(logp && pos && scores && seqs && words && hyp_score && hyp_len && hyp_seq && done && n_done && B > 0 && max_len > 1,
+              "hf_beam_step: null/empty");
+  EVK_REQUIRE((int64_t)B * nb * (int64_t)max_len < INT32_MAX && (!anc || anc_cols > 0), "hf_beam_step: bad state geometry");
+  EVK_REQUIRE(!pos_advance || ticket, "hf_beam_step: advancing the position needs a (zero-initialised) ticket word");
+  const size_t lds = (size_t)nb * max_len * 8 + (anc ? (size_t)nb * anc_cols * 4 : 0);
+  EVK_REQUIRE(lds <= 48000, "hf_beam_step: %zu bytes of per-study state do not fit the staging buffer", lds);
+  HfBeamP p{logp, ld, V, nb, max_len, eos, pad, force_end, reinterpret_cast<const long long*>(pos), scores, reinterpret_cast<long long*>(seqs),
+            reinterpret_cast<long long*>(words), anc, anc_cols, hyp_score, hyp_len, reinterpret_cast<long long*>(hyp_seq), done, n_done,
+            reinterpret_cast<long long*>(pos_advance), ticket};
+  ProfScope ps(EVK_FAM_NORM, s);
+  if (nb <= 2) hipLaunchKernelGGL(hf_beam_step_kernel<4>, dim3(B), dim3(256), lds, s, p);
+  else if (nb <= 4) hipLaunchKernelGGL(hf_beam_step_kernel<8>, dim3(B), dim3(256), lds, s, p);
+  else hipLaunchKernelGGL(hf_beam_step_kernel<16>, dim3(B), dim3(256), lds, s, p);
+  return evk_check_launch("hf_beam_step");
+}
+
+}  // extern "C"

@@ -476,11 +476,18 @@ class _Session:
     (13 ms of host time per 64-study batch otherwise, during which the decode stream sits idle).  A subclass supplies _body() (the
     launches of one token step) and _run_iter() (what happens around the token loop)."""
 
+    def _init_driving(self, dec, slot):
+        """what _drive, run_iter and __del__ read whatever the backend: every subclass calls this, also one that allocates buffers of its own
+        (gpt2_decode._GPT2Session).  Beyond these, _drive needs words, ticket, pos and logp_buf on the device."""
+        self.dec, self.slot = dec, slot
+        self.graph = self.plan = None     # the captured per-token step and its replay plan
+        self.issued = 0                   # bodies issued by the last _drive, warm-up included
+
     def __init__(self, dec, B, R, max_len, S, dev, slot=0):
         model = dec.model
-        self.slot = slot
+        self._init_driving(dec, slot)
         d, nl = model.d_model, len(model.decoder.layers)
-        self.dec, self.B, self.max_len, self.R = dec, B, max_len, R
+        self.B, self.max_len, self.R = B, max_len, R
         self.kc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
         self.vc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
         self.st = None                    # R-row decoder state, built on first use (needs an encoder output for its geometry)
@@ -488,7 +495,6 @@ class _Session:
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pos = torch.ones(1, dtype=torch.long, device=dev)
         self.logp_buf = torch.empty(R, dec.vocab_size + 1, dtype=F32, device=dev)
-        self.graph = self.plan = None
         self.fused_key = None
         # the encoder key mask of the CURRENT batch, in a buffer the session owns: the captured per-token step records a pointer, so a
         # later batch's mask must land at the same address (a session serves masked or unmasked batches, never both: part of its key)
@@ -563,10 +569,11 @@ class _Session:
         self.st.enc, self.st.src_mask = enc, src_mask
         return src_mask
 
-    def _drive(self, n_body, first, step_hook, burst, extra=()):
+    def _drive(self, n_body, first, step_hook, burst, extra=(), stop=None):
         """the token loop: n_body times _body(), body number i writing the log-probabilities of position i + first (step_hook(position,
         logp_buf, *extra) is called right after it).  On first use two bodies run as warm-up, the third is captured and turned into a
-        replay plan; the loop then replays.  A generator: yields after every issued step (see _run_iter of the subclasses)."""
+        replay plan; the loop then replays.  A generator: yields after every issued step (see _run_iter of the subclasses).
+        stop(i) (optional, host only): asked before body number i (or the burst that starts with it) is issued; True ends the loop there."""
         dev = self.logp_buf.device
         done = 0
         cur = torch.cuda.current_stream()
@@ -624,11 +631,17 @@ class _Session:
         ev0.record()
         it_ = done
         while bursts and it_ < n_body:
+            if stop is not None and stop(it_):
+                n_body = it_
+                break
             n = min(int(burst), n_body - it_)
             H.check(H.lib.evk_replay_run_n(self.plan, H.stream(), n), 'replay_run_n')
             it_ += n
             yield it_ - 1
         for it_ in range(it_, n_body):
+            if stop is not None and stop(it_):
+                n_body = it_
+                break
             if self.plan is not None:
                 H.check(H.lib.evk_replay_run(self.plan, H.stream()), 'replay_run')
             elif self.graph is not None:
@@ -640,6 +653,7 @@ class _Session:
             yield it_
         ev1.record()
         stats['step_events'] = (ev0, ev1, max(0, n_body - done))      # per-token step time = elapsed / count (bench.py)
+        self.issued = max(n_body, done)                                  # bodies issued, warm-up included
         stats['graph'] = self.graph is not None
         stats['replayer'] = self.plan is not None
         stats['fused_bookkeeping'] = True

@@ -134,6 +134,7 @@ class DistilGPT2TextDecoderModel(nn.Module):
         self.bos_token_id = tokenizer.token_to_id('[BOS]')
         self.beam_size = config['beam_size']
         self.max_seq_len = config['max_seq_len']
+        self.sample_n = int(config.get('sample_n', 1))         # default of generate(num_return_sequences=...)
         self.p_embd = 0.1
 
     @property
@@ -161,15 +162,47 @@ class DistilGPT2TextDecoderModel(nn.Module):
             return ops.nll_loss(lg, input_ids.reshape(-1), w.reshape(-1), self.vocab)
         return self.generate(encoder_hidden_states)
 
+    def session_available(self, S=None):
+        """generate() takes the device route (evoke_amd/gpt2_decode.py) for this decoder (and an encoder output of S positions)"""
+        from .gpt2_decode import session_usable
+        return session_usable(self, S)
+
     @torch.no_grad()
-    def generate(self, enc):
-        """HF beam search (num_beams = beam_size, max_length = max_seq_len, length_penalty 1, early_stopping False)."""
+    def generate(self, enc, num_return_sequences=None, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0):
+        """HF beam search (num_beams = beam_size in 1..8, max_length = max_seq_len, length_penalty 1, early_stopping False) -> (B * n, L) ids
+        starting with [BOS], padded with [PAD], L = min(longest, max_seq_len): the n = num_return_sequences (default: config sample_n, 1)
+        best hypotheses of every study next to each other; with return_scores also their scores (B * n,) f64 = HF's sequences_scores.
+        The search runs on the device (gpt2_decode: one captured step per token, no host synchronisation in the loop) whenever it can:
+        head size 64 / 128 / 256, 5 <= max_seq_len <= 256, graph capture enabled, EVK_GPT2_SESSION not '0'.  Otherwise the host-driven
+        loop (_generate_host), which serves beam_size <= 4 and n = 1 only and refuses the rest with NotImplementedError.
+        step_hook(t, logp, scores): test instrument, called on the launching stream before the bookkeeping of position t reads `logp`
+        (f32 (B * beam, V), may be edited in place); slot / as_iterator / burst: as decode.beam_search -- the iterator returns the packed
+        result of gpt2_decode._GPT2Session._run_iter."""
+        nb = int(self.beam_size)
+        if not 1 <= nb <= 8:
+            raise ValueError('beam_size must be in [1, 8] for the distilgpt2 backend, not %d' % nb)
+        n = self.sample_n if num_return_sequences is None else int(num_return_sequences)
+        if not 1 <= n <= nb:
+            raise ValueError('num_return_sequences must be in [1, beam_size = %d], not %d' % (nb, n))
+        if self.vocab < 2 * nb:
+            raise ValueError('the vocabulary must hold 2 * beam_size candidates')
+        if self.session_available(enc.shape[1]):
+            from . import gpt2_decode
+            return gpt2_decode.search(self, enc, n, return_scores, step_hook, slot, as_iterator, burst)
+        if nb > 4 or n > 1 or return_scores or as_iterator or step_hook is not None:
+            raise NotImplementedError('beam_size > 4, num_return_sequences > 1, scores, step hooks and stepwise iteration need the device '
+                                      'route of the distilgpt2 search')
+        return self._generate_host(enc)
+
+    @torch.no_grad()
+    def _generate_host(self, enc):
+        """the search driven from the host (two device -> host copies per token): the route of geometries the device session does not serve"""
         was_training = self.training
         self.eval()
         try:
             nb, max_len, V = self.beam_size, self.max_seq_len, self.vocab
             if 2 * nb > 8:
-                raise ValueError('beam_size must be <= 4 for the distilgpt2 backend')
+                raise NotImplementedError('the host-driven search serves beam_size <= 4')
             B, dev, d = enc.shape[0], enc.device, enc.shape[-1]
             encx = enc.repeat_interleave(nb, dim=0).contiguous()
             R = B * nb

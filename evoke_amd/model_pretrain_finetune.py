@@ -188,17 +188,27 @@ class FineTune(_Base):
         loop to the launch queue from native code (evk_replay_run_n: the interpreter is not on the per-token path, the GIL is free);
         this thread meanwhile queues the visual extractor / fusion / text encoders of the following batch on a further stream.  Per batch the
         kernels, their order and therefore the results are exactly those of forward() (tests/test_model_gpu.py).  batches: iterable of
-        (images, report_ids, report_masks, patient_ids, inc_ids, inc_masks).  depth: EVK_DECODE_DEPTH or 4.  (The distilgpt2 backend has no
-        stepwise sessions: for it only the encoders run ahead, _generate_encoders_ahead.)"""
+        (images, report_ids, report_masks, patient_ids, inc_ids, inc_masks).  depth: EVK_DECODE_DEPTH or 4.  Both decoder backends take this
+        route; a distilgpt2 decoder without a device session (gpt2_decode.session_usable: head size, max_seq_len, capture, EVK_GPT2_SESSION)
+        falls back to _generate_encoders_ahead.  The encoder length S is known only per batch: a batch with S > 256 on a decoder that has a
+        session runs its host-driven search in one go inside this loop, and that search raises NotImplementedError for beam_size > 4 or
+        sample_n > 1 (DistilGPT2TextDecoderModel.generate)."""
         import os
         from collections import deque
         if mode not in ('sample', 'inference'):
             raise ValueError
-        if self.decoder_kind != 'r2gen':
+        gpt2 = self.decoder_kind != 'r2gen'
+        if gpt2 and not self.text_decoder.session_available():
             yield from self._generate_encoders_ahead(batches, mode)
             return
         from .decode import beam_search, sample
-        if decode_route(self.args) == 'beam':
+        if gpt2:
+            # decode.beam_search's calling convention over DistilGPT2TextDecoderModel.generate (the encoder mask is not used: HF ignores the
+            # field the reference passes it in); the stepwise search returns its result packed, trimmed in finish() once it is on the host
+            def search(dec, x, enc_mask, args, slot=0, as_iterator=False, burst=0):
+                return dec.generate(x, slot=slot, as_iterator=as_iterator, burst=burst)
+            result = (lambda v: v)
+        elif decode_route(self.args) == 'beam':
             search, result = beam_search, (lambda v: v)
         else:
             search, result = sample, (lambda v: v[0])            # (seq, seq_logprobs): the ids
@@ -258,9 +268,9 @@ class FineTune(_Base):
                 enc_mask.record_stream(dec_s[slot])
                 try:
                     gen = search(self.text_decoder, x, enc_mask, self.args, slot=slot, as_iterator=True, burst=burst if threaded else 0)
-                    job = [slot, gen, report_ids, None, None, None]
+                    job = [slot, gen, report_ids, None, None, None, gpt2]
                 except NotImplementedError:              # no session path for this geometry: the whole search in one go
-                    return [slot, None, report_ids, result(search(self.text_decoder, x, enc_mask, self.args)), None, None]
+                    return [slot, None, report_ids, result(search(self.text_decoder, x, enc_mask, self.args)), None, None, False]
                 if threaded:
                     # everything in front of the token loop (cross-attention K / V, position 0, on first use the graph capture, which
                     # must not meet another thread's allocations) from THIS thread; the loop itself from a worker
@@ -306,6 +316,9 @@ class FineTune(_Base):
             if job[4] is None:
                 with torch.cuda.stream(dec_s[job[0]]):
                     job[4] = seq.cpu()               # waits for that decode stream only
+            if job[6]:                               # (distilgpt2, stepwise: packed ids | length -> the ids up to the longest hypothesis)
+                from .gpt2_decode import unpack
+                seq, job[4] = unpack(seq, job[4]), unpack(job[4])
             ops.check_forward_guard(seq.device)      # verdicts of the encoder passes that have finished
             gen_texts = self.tokenizer.decode_batch(job[4].tolist())
             gen_texts = [t if len(t) > 0 else NO_FINDING for t in gen_texts]

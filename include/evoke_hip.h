@@ -428,6 +428,16 @@ int evk_decode_attention_indirect(const void* q, const void* k, const void* v, c
  * (encoder_decoder.py:182-214 driven by caption_model.py:beam_search) without a copy kernel.  rowmap[r][*last_pos] must be r. */
 int evk_decode_attention_qkv(const void* qkv, int64_t ldq, void* k_cache, void* v_cache, const int32_t* rowmap, const int64_t* last_pos, void* out,
                              int32_t R, int32_t S, int32_t heads, int32_t head_dim, float scale, evk_stream_t stream);
+/* The single-query attention for head_dim 128 and 256 (decode_attn_wide.hip; the 2048-wide, 8-head decoder of the EVOKE YAML files), one
+ * entry point for what the three above take at head_dim 64: q bf16 [R][ldq] read in place (ldq 0 = heads * head_dim, else a multiple of
+ * 8, e.g. a fused q | k | v row), k / v bf16 [R/kv_div][S][heads * head_dim], mask uint8 [R/kv_div][S] or NULL, rowmap int32 [R][S] or
+ * NULL (kv_div 1), last_pos device int64 scalar or NULL (positions beyond it are neither read nor attended), knew / vnew bf16 [R][ldq]
+ * or NULL (this step's key / value: attended to as position *last_pos and appended to row r of the caches; needs last_pos, kv_div 1;
+ * with a rowmap, rowmap[r][*last_pos] must be r, as for evk_decode_attention_qkv).
+ * f32 online softmax, S <= 256, every operand 16-byte aligned.  head_dim 64 is refused: it keeps its own kernel. */
+int evk_decode_attention_wide(const void* q, int64_t ldq, void* k, void* v, const void* knew, const void* vnew, const unsigned char* mask,
+                              const int32_t* rowmap, const int64_t* last_pos, void* out, int32_t R, int32_t S, int32_t heads, int32_t head_dim,
+                              int32_t kv_div, float scale, evk_stream_t stream);
 int evk_log_softmax_nll_fwd(const float* logits, float* logp, float* lse, const int64_t* target, const float* wmask, float* acc2,
                             int64_t rows, int32_t V, int32_t ld, int32_t ld_out, evk_stream_t stream);
 /* logp [rows][ld_out] = log_softmax(logits * scale) over the V valid columns: the temperature of the beam search's later steps,
@@ -499,6 +509,25 @@ int evk_beam_step_opts(const float* logp, int32_t ld, int32_t V1, int32_t beam, 
  * finished list (take = 1 or beam): out[row][t] = hist[t][fin_anc[b][k][t]] for t < fin_len[b][k], zeros beyond.  One launch after the search. */
 int evk_beam_gather_logprobs(const float* hist, const int32_t* fin_anc, const int32_t* fin_len, float* out, int32_t B, int32_t beam,
                              int32_t take, int32_t max_len, int32_t V1, evk_stream_t stream);
+/* One launch for everything the distilgpt2 backend's search does between two decoder steps (hf_beam.hip): Hugging Face's classic
+ * BeamSearchScorer at length_penalty 1, early_stopping False, which language_model.py:271-280 reaches through `generate` and
+ * oracle/gpt2.py:120-186 restates.  One workgroup per study; nb = num_beams in [1, 8], V >= 2 * nb, ld >= V.
+ *   logp f32 [B*nb][ld]; *pos = last filled column of seqs, cur_len = *pos + 1 = generated tokens including an [EOS] of this step.
+ *   Candidates scores[b][src] + logp[b*nb+src][w] (f32 add); the 2 * nb largest in descending order, ties to the lowest flat index.
+ *   Rank walk: an eos candidate at rank < nb enters the study's hypothesis list with score (double)sum / cur_len, one at rank >= nb is
+ *   skipped, the first nb others become the next beams.  List: hyp_score f64 [B][nb], hyp_len int32 [B][nb] (columns; 0 = empty slot,
+ *   zeroed by the caller before the first step), hyp_seq int64 [B][nb][max_len] with the leading [BOS], padded with `pad`; sorted by score
+ *   descending, ties keep the earlier entry in front, cut to nb.  done uint8 [B]: set when the list is full and
+ *   hyp_score[nb-1] >= (double)(rank-0 candidate) / cur_len; *n_done (int32) += studies that became done in this launch.  A done study
+ *   emits `pad` with zero scores, takes every beam from its first row and never touches its list again.
+ *   In place, in the winners' order: seqs int64 [B*nb][max_len] (new token in column *pos + 1), anc int32 [B*nb][anc_cols] or NULL (the
+ *   cache row table; column *pos + 1 is then seeded with each row's own index); out: words int64 [B*nb], scores f32 [B][nb].
+ *   force_end != 0 (the last position): after the step every study that is not done appends its nb new beams, sum / cur_len.
+ *   pos_advance / ticket as in evk_beam_step. */
+int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                     int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
+                     double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
+                     int32_t* ticket, evk_stream_t stream);
 /* One launch for everything AttModel._sample does between two decoder steps (sample.hip; modules/att_model.py:176-221 and
  * CaptionModel.sample_next_word, modules/caption_model.py:363-401), for R independent rows.  logp [R][ld] f32 log-probs (V1 = V+1 valid
  * columns, V1 <= 4096); *pos = position t being written.  In the reference's order: decoding_constraint != 0 and t > 0: column seq[r][t-1]

@@ -1,0 +1,64 @@
+"""Beam search of the distilgpt2 decoder backend, timed: 32 studies x 50 encoder positions, the decoder sizes of the EVOKE YAML files
+(3 layers x 2048 x 8 heads), beam 3, max_seq_len 100, procedural weights.  Two warm-up calls, then three timed runs of
+DistilGPT2TextDecoderModel.generate(); per run: wall seconds, tokens/s (studies x generated positions of the returned ids / seconds), and --
+where the search runs as a device session -- the per-token step time from the HIP events of the token loop and the launches of one
+captured step.  Uses only the public generate(), so the same file measures a commit from before the device session.
+
+    python tools/gpt2_decode_bench.py [--studies 32] [--beam 3] [--max-seq-len 100] [--runs 3]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--studies', type=int, default=32)
+    ap.add_argument('--beam', type=int, default=3)
+    ap.add_argument('--max-seq-len', type=int, default=100)
+    ap.add_argument('--runs', type=int, default=3)
+    a = ap.parse_args()
+    from evoke_amd import decode, ops
+    from evoke_amd.config import ARGS
+    from evoke_amd.gpt2 import DistilGPT2TextDecoderModel
+    from evoke_amd.tokenizer import load_tokenizer
+    from oracle import gpt2 as G, spec as S
+    V, d, layers, heads = 1444, 2048, 3, 8
+    tok = load_tokenizer(os.path.join(REPO, 'tests', 'golden', 'iu_xray_wordlevel_uncased_tokenizer.json'))
+    args = dict(ARGS, decoder_hidden_size=d, decoder_num_hidden_layers=layers, decoder_num_attention_heads=heads, beam_size=a.beam,
+                max_seq_len=a.max_seq_len)
+    dec = DistilGPT2TextDecoderModel(args, tok)
+    sd = {k[len('text_decoder.'):]: v for k, v in S.procedural_state(G.gpt2_spec(V, d, layers)).items()}
+    sd['decoder.encoder_decoder.decoder.lm_head.weight'] = sd['decoder.encoder_decoder.decoder.transformer.wte.weight']
+    dec.load_state_dict(sd)
+    dec = dec.cuda().eval()
+    ops.set_dropout_enabled(False)
+    enc = (S.det((a.studies, 50, d), a=.013, b=.007, c=.3) * 0.5).to(ops.BF16).cuda()
+    runs = []
+    for i in range(2 + a.runs):
+        decode.stats.pop('step_events', None)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        seq = dec.generate(enc)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        rec = dict(seconds=round(dt, 4), width=int(seq.shape[1]), tokens_per_s=round(a.studies * (seq.shape[1] - 1) / dt, 1))
+        ev = decode.stats.get('step_events')
+        if ev is not None and ev[2] > 0:
+            rec['step_ms'] = round(ev[0].elapsed_time(ev[1]) / ev[2], 4)
+            rec['step_launches'] = decode.stats.get('step_launches')
+            rec['steps_issued'] = decode.stats.get('gpt2_steps_issued')
+        if i >= 2:
+            runs.append(rec)
+    print(json.dumps(dict(studies=a.studies, beam=a.beam, max_seq_len=a.max_seq_len, device_session=bool(getattr(dec, 'session_available', lambda *_: False)(50)),
+                          runs=runs)))
+
+
+if __name__ == '__main__':
+    main()
