@@ -7,30 +7,30 @@ steps) and walks a per-sample Python loop with .item() syncs; this engine is mat
 incremental: per-layer self-attention K/V caches, cross-attention K/V projected once, the relational memory carried
 as state, the per-position conditional-LayerNorm inputs taken from the current memory, and all beam bookkeeping
 (segmented top-k, EOS handling, the -1000 penalty, best-finished-beam tracking) done on the device.
+
+Two tiers.  The SESSION (_Session and its subclasses, gpt2_decode._GPT2Session) keeps every buffer of a batch geometry on the decoder and
+owns the one token-loop driver, _Session._drive: warm-up, capture of the per-token launch sequence, the replay plan, bursts -- or, with
+_GRAPH_ENABLED off, the same launches issued eagerly.  Geometries its kernels do not serve (head dim other than 64, more than 256
+positions) and EVK_DECODE_SESSION=0 take a plain HOST LOOP around _DecoderState.step(): _beam_eager and _sample_eager.
 """
 import ctypes as C
-import os
-from .config import tunable
-import threading
 import math
+import os
+import threading
+import warnings
+import weakref
 
 import torch
 
 from . import hip as H
 from . import ops
+from .config import tunable
 from .ops import BF16, F32
 
-_INDIRECT = [tunable('EVK_DECODE_INDIRECT', '1') != '0']      # beam search re-orders a row table, not the K/V caches
-_GRAPH_ENABLED = [True]          # capture the per-token launch sequence in a HIP graph (set False to debug eagerly)
-_FUSED_APPEND = [tunable('EVK_DECODE_FUSED_APPEND', '1') != '0']  # K / V cache append + strided q inside the self-attention kernel
-# decoder norms applied in the operand load of the projection that follows (evk_linear_ln): 'off' (default), 'final' = only the unconditional last norm in
-# front of the logits -- measured 0.489 -> 0.499 ms per token: 16 rows x 2 dependent wave reductions per wave cost more than the norm launch --,
-# 'all' = the nine conditional norms too -- measured 0.49 -> 0.64 ms per token: every one of the
-# N/16 workgroups of a projection re-reads its 64 rows of per-hypothesis gamma / beta deltas, 128 KB against a 64 KB activation tile, and a
-# workgroup's loads are bound by one CU's L1 fill rate (DESIGN.md section 3).  The entry point stays (bit-identical to norm + GEMM, tested).
-_FUSED_LN = [tunable('EVK_DECODE_FUSED_LN', 'off')]
+# capture the per-token launch sequence in a HIP graph; False (read at every search): the session issues the same launches eagerly (debugging)
+_GRAPH_ENABLED = [True]
+_SESSION = [tunable('EVK_DECODE_SESSION', '1') != '0']           # the persistent session; off: the host loops (_beam_eager, _sample_eager)
 _SPLIT_CLN = [tunable('EVK_DECODE_SPLIT_CLN', '1') != '0']       # first conditional-norm MLP layer as two launches (see cln_deltas)
-_FUSED_BOOK = [tunable('EVK_DECODE_FUSED_BOOK', '1') != '0']      # beam bookkeeping as one kernel per token (csrc/beam.hip)
 # relational memory of the decode step in f32 (csrc/rm_f32.hip) -- the DEFAULT since round 4: the engine's log-probabilities stay within 5.3e-3 of
 # the reference's at ALL 100 positions of the config-5 golden (the 16-bit recurrence: 2e-3 at position 10, 0.5 at position 90).  EVK_DECODE_RM_F32=0
 # selects the 16-bit recurrence (evk_rm_decode_step), which drifts at depth and is kept for comparison only.
@@ -45,26 +45,14 @@ _PLANS = []                      # (plan, graph, event recorded after the last r
 
 
 _cap_streams = {}
-_pools = {}
-_last_graph = {}                 # device -> the most recent captured graph: keeps the shared memory pool referenced between batches
 
 
-def _capture_stream(dev, kind='capture'):
+def _capture_stream(dev, kind):
     key = (torch.device(dev).index, kind)
     st = _cap_streams.get(key)
     if st is None:
         st = _cap_streams[key] = torch.cuda.Stream(device=dev)
     return st
-
-
-def _graph_pool(dev, slot=0):
-    """ONE private memory pool for the per-token graphs of every generate call on a device: a fresh pool per capture means a
-    hipMalloc per batch (and a hipFree when the graph dies), and those synchronise the whole device -- which serialises the decode of
-    batch k behind the encoders of batch k+1 that FineTune.generate_pipelined runs on another stream."""
-    key = (torch.device(dev).index, slot)          # (searches in flight at the same time replay concurrently: a pool each)
-    if key not in _pools:
-        _pools[key] = torch.cuda.graph_pool_handle()
-    return _pools[key]
 
 
 _plans_lock = threading.Lock()    # (searches driven by host threads end at the same time)
@@ -93,23 +81,13 @@ def _topk(x, k):
     return vals, idx
 
 
-def _attend1(q, k, v, heads, mask, rowmap=None, last_pos=None):
+def _attend1(q, k, v, heads, mask):
     """One-query attention: q (R, 1, H*dh); k / v (R/div, S, H*dh) and mask uint8 (R/div, S) or None, where `div` consecutive
-    query rows (the beams of one sample) share a K / V row -> (R, 1, H*dh).  rowmap int32 (R, S): position s of hypothesis r
-    lives in cache row rowmap[r, s] (beam search that re-orders the index table instead of the caches)."""
+    query rows (the beams of one sample) share a K / V row -> (R, 1, H*dh)."""
     R = q.shape[0]
     Rk, S, HD = k.shape
     dh = HD // heads
     div = R // Rk
-    if rowmap is not None:
-        if dh != 64 or S > 256 or div != 1:
-            raise NotImplementedError('cache indirection needs head_dim 64, S <= 256')
-        out = torch.empty_like(q)
-        H.check(H.lib.evk_decode_attention_indirect(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask) if mask is not None else None, H.ptr(rowmap),
-                                                    H.ptr(last_pos) if last_pos is not None else None, H.ptr(out), R, S, heads, dh,
-                                                    C.c_float(1.0 / math.sqrt(dh)), H.stream()),
-                'decode_attention_indirect')
-        return out
     if dh != 64 or S > 256:
         if div > 1:
             k, v = k.repeat_interleave(div, 0), v.repeat_interleave(div, 0)
@@ -210,25 +188,6 @@ class _FusedDecodeWeights:
                                           H.ptr(sync) if sync is not None else None, H.stream()), 'decode_rowblock')
         return y, n
 
-    def ln_linear(self, x, gamma, beta, eps, w, bias, N, deltas=None, act=H.ACT_NONE, resid=None, out_f32=False):
-        """act(LayerNorm(x) @ w^T + bias) (+ resid) in ONE launch (evk_linear_ln: the norm runs in the GEMM's operand load); x (R, 512)
-        16-bit, w (>= N rows, 512) 16-bit, deltas = (dgam, dbet) rows of the conditional norm or None.  Output (R, pad8(N))."""
-        R, K = x.shape[0], x.shape[-1]
-        Np = (N + 7) // 8 * 8
-        mk = torch.zeros if Np != N else torch.empty
-        y = mk(R, Np, dtype=torch.float32 if out_f32 else BF16, device=x.device)
-        dg, db = deltas if deltas is not None else (None, None)
-        H.check(H.lib.evk_linear_ln(H.ptr(x), H.ptr(gamma), H.ptr(beta), H.ptr(dg) if dg is not None else None, H.ptr(db) if db is not None else None,
-                                    dg.stride(0) if dg is not None else 0, C.c_float(eps), 1, H.ptr(w), H.ptr(bias) if bias is not None else None,
-                                    H.ptr(resid) if resid is not None else None, Np, H.ptr(y), H.F32 if out_f32 else H.BF16, Np, R, N, K, act,
-                                    H.stream()), 'linear_ln')
-        return y
-
-    def cln_linear(self, i, x, deltas, w, bias, N, act=H.ACT_NONE):
-        """conditional norm i of the decoder followed by a projection"""
-        c = self.clns[i]
-        return self.ln_linear(x, self.geff[i], self.beff[i], c.eps, w, bias, N, deltas=(deltas[2 * i], deltas[2 * i + 1]), act=act)
-
     def qkv(self, li, n):
         R, d = n.shape[0], self.d
         out = torch.empty(R, 3 * d, dtype=BF16, device=n.device)
@@ -251,16 +210,22 @@ def _fused_weights(model):
 class _DecoderState:
     """Incremental state of R = batch*beam hypotheses."""
 
-    def __init__(self, dec, enc, src_mask, max_len, cross_kv=None, rows=None):
+    def __init__(self, dec, enc, src_mask, max_len, cross_kv=None, rows=None, row_table=False):
         """cross_kv: ([K per layer], [V per layer]) already projected from `enc` (the session computes them once for both the first,
-        B-row step and the R-row steps); rows: hypothesis count of the self-attention caches / memory (default: enc rows)."""
+        B-row step and the R-row steps); rows: hypothesis count of the self-attention caches / memory (default: enc rows); row_table:
+        build the cache row table that step_static needs (a session's R-row state; head dim 64, max_len <= 256)."""
         model = dec.model
         self.dec, self.model = dec, model
         R, d = (enc.shape[0] if rows is None else rows), model.d_model
         self.enc, self.src_mask = enc, src_mask
         self.mem = model.rm.init_memory(R, enc.device)
         self.t = 0
-        self.anc = self.rows = None      # cache row table of the graph-mode steps (step_static)
+        # cache row table of step_static: position s of hypothesis r lives in cache row anc[r, s], so that a beam search re-orders
+        # this table (100 KB) and not the self-attention caches (6 x 26 MB gathered and copied)
+        self.anc = self.rows = None
+        if row_table:
+            self.rows = torch.arange(R, dtype=torch.int32, device=enc.device).view(R, 1)
+            self.anc = self.rows.expand(R, max_len).contiguous()
         self.logit_scale = 1.0           # 1 / temperature of the beam search's later steps (step_static only; caption_model.py:196)
         self.tmem = None                 # tanh(memory), kept beside the memory by the session path (evk_rm_decode_step)
         # the f32 relational memory (evk_rm_decode_step_f32): the state, the unrounded token embedding, scratch, the 16-bit row for the decoder
@@ -290,9 +255,16 @@ class _DecoderState:
                                              H.ptr(self.rm32_ws), self.rm32_ws.numel(), Rh, H.stream()), 'rm_decode_step_f32')
         return self.rm32_out
 
+    def expand_cross(self, n):
+        """n hypotheses per sample for the host-position step(), whose attention wants one K / V row per query row (step_static reads
+        one row per SAMPLE instead: evk_decode_attention kv_div)"""
+        self.kc = [k.repeat_interleave(n, 0) for k in self.kc]
+        self.vc = [v.repeat_interleave(n, 0) for v in self.vc]
+        self.src_mask = self.src_mask.repeat_interleave(n, 0) if self.src_mask is not None else None
+
     def reorder(self, ix):
         """first beam expansion (B -> B*beam hypotheses).  The encoder states, their mask and the cross-attention K/V stay at
-        one row per SAMPLE: every beam of a sample reads the same row (evk_decode_attention kv_div)."""
+        one row per SAMPLE: every beam of a sample reads the same row (evk_decode_attention kv_div; step() needs expand_cross)."""
         self.mem = self.mem.index_select(0, ix)
         if self.mem32 is not None:
             self.mem32 = self.mem32.index_select(0, ix)
@@ -313,33 +285,24 @@ class _DecoderState:
                 self.ks[i][:, :t] = self.ks[i][:, :t].index_select(0, ix)
                 self.vs[i][:, :t] = self.vs[i][:, :t].index_select(0, ix)
 
-    def reorder_static(self, ix):
-        """reorder() for a hypothesis count that no longer changes: every buffer is updated in place (graph-capturable)."""
-        # ix only permutes hypotheses WITHIN a sample (state_ix = beam_ix + sample * beam): the encoder states, their mask and
-        # the cross-attention K/V are identical for all beams of a sample and need no reordering once expanded
-        self.mem.copy_(self.mem.index_select(0, ix))
-        if self.mem32 is not None:
-            self.mem32.copy_(self.mem32.index_select(0, ix))
-        if self.anc is not None:
-            # the self-attention caches stay where they are: hypothesis r inherits the ROW TABLE of its parent (position s of
-            # r lives in the cache row of the ancestor that wrote it) -- 100 KB moved instead of 6 x 26 MB gathered and copied
-            self.anc.copy_(self.anc.index_select(0, ix))
-            return
-        for i in range(len(self.ks)):
-            self.ks[i].copy_(self.ks[i].index_select(0, ix))
-            self.vs[i].copy_(self.vs[i].index_select(0, ix))
+    def _self_attend(self, i, qkv, pos):
+        """self-attention of layer i over the row table: q read in place from qkv (R, q | k | v), this step's K / V attended to straight
+        from qkv and appended to the caches at position *pos by the same kernel -> (R, 1, d)"""
+        d = self.model.d_model
+        h = self.model.decoder.layers[0].self_attn.h
+        c = torch.empty(qkv.shape[0], 1, d, dtype=qkv.dtype, device=qkv.device)
+        H.check(H.lib.evk_decode_attention_qkv(H.ptr(qkv), qkv.stride(0), H.ptr(self.ks[i]), H.ptr(self.vs[i]), H.ptr(self.anc), H.ptr(pos),
+                                               H.ptr(c), qkv.shape[0], self.ks[i].shape[1], h, d // h, C.c_float(1.0 / math.sqrt(d // h)),
+                                               H.stream()), 'decode_attention_qkv')
+        return c
 
-    def step_static(self, it, pos, kmask, out=None, seed_rows=True):
-        """step() with the position held in a device tensor `pos` (1,) and self-attention over the whole cache under the key
-        mask `kmask` (R, max_len; 1 for positions <= pos): no host-side shape depends on the step index, so the launch
-        sequence can be captured once in a HIP graph and replayed."""
+    def step_static(self, it, pos, out=None, seed_rows=True):
+        """step() with the position held in a device tensor `pos` (1,) and self-attention over the cache row table (positions <= *pos,
+        read from the device): no host-side shape depends on the step index, so the launch sequence can be captured once in a HIP graph
+        and replayed.  Needs a state built with row_table=True."""
         model = self.model
         h = model.decoder.layers[0].self_attn.h
-        if self.anc is None and _INDIRECT[0] and model.d_model // h == 64 and self.ks[0].shape[1] <= 256:
-            R_, S_ = self.ks[0].shape[0], self.ks[0].shape[1]
-            self.rows = torch.arange(R_, dtype=torch.int32, device=pos.device).view(R_, 1)
-            self.anc = self.rows.expand(R_, S_).contiguous()
-        if self.anc is not None and seed_rows:
+        if seed_rows:
             self.anc.index_copy_(1, pos, self.rows)      # this step's K / V are written to the hypothesis's own cache row
         # the positional row is picked on the device (pos is a device scalar inside the captured step)
         emb = ops.embedding(it.view(-1, 1).contiguous(), model.tgt_embed[0].lut.weight, pos=model.tgt_embed[1].pe[0], scale=math.sqrt(model.d_model),
@@ -362,12 +325,8 @@ class _DecoderState:
             memory, new_mem = model.rm.run(emb, self.mem)
             ops.copy_kernel(self.mem, new_mem)
         deltas = fw.cln_deltas(memory)
-        x = emb
-        ln_ok = d == 512 and x.shape[0] <= 4096
-        fuse_ln = _FUSED_LN[0] == 'all' and ln_ok
-        x = x.view(-1, d)
-        rb = fw.rb if (fw.rb is not None and not fuse_ln and self.anc is not None and x.is_contiguous()) else None
-        n_final = None
+        x = emb.view(-1, d)
+        rb = fw.rb if x.is_contiguous() else None
         if rb is not None:
             # row-block path: 6 launches per layer -- q|k|v, self-attention, [o-proj + residual + norm], q, cross-attention, [o-proj + residual +
             # norm], [feed-forward + residual + next norm]
@@ -378,64 +337,31 @@ class _DecoderState:
             n = fw.norm(0, x, deltas).view(-1, d)
             for i, layer in enumerate(model.decoder.layers):
                 w = rb[i]
-                qkv = fw.qkv(i, n)
-                c = torch.empty(qkv.shape[0], 1, d, dtype=qkv.dtype, device=qkv.device)
-                H.check(H.lib.evk_decode_attention_qkv(H.ptr(qkv), qkv.stride(0), H.ptr(self.ks[i]), H.ptr(self.vs[i]), H.ptr(self.anc), H.ptr(pos),
-                                                       H.ptr(c), qkv.shape[0], self.ks[i].shape[1], h, d // h, C.c_float(1.0 / math.sqrt(d // h)),
-                                                       H.stream()), 'decode_attention_qkv')
+                c = self._self_attend(i, fw.qkv(i, n), pos)
                 x, n = fw.rowblock(c.view(-1, d), x, w['so'], w['so_b'], 3 * i + 1, deltas, sync=self.rb_sync)
                 q = layer.src_attn.linears[0](n)
                 c = _attend1(q.view(-1, 1, d), self.kc[i], self.vc[i], h, self.src_mask)
                 x, n = fw.rowblock(c.view(-1, d), x, w['co'], w['co_b'], 3 * i + 2, deltas, sync=self.rb_sync)
                 x, n = fw.rowblock(n, x, w['w2'], w['b2'], 3 * (i + 1) if i + 1 < nl else None, deltas, w1=w['w1'], b1=w['b1'], sync=self.rb_sync)
-            n_final = n
-        for i, layer in enumerate(model.decoder.layers if rb is None else ()):
-            sa = layer.self_attn
-            if fuse_ln:
-                qkv = fw.cln_linear(3 * i, x, deltas, fw.qkv_w[i], fw.qkv_b[i], 3 * d)
-            else:
-                n = fw.norm(3 * i, x, deltas)
-                qkv = fw.qkv(i, n.view(-1, d))
-            if self.anc is not None and _FUSED_APPEND[0] and qkv.stride(0) % 8 == 0:
-                # q read in place, this step's K / V attended to straight from qkv and appended to the caches by the same kernel
-                c = torch.empty(qkv.shape[0], 1, d, dtype=qkv.dtype, device=qkv.device)
-                H.check(H.lib.evk_decode_attention_qkv(H.ptr(qkv), qkv.stride(0), H.ptr(self.ks[i]), H.ptr(self.vs[i]), H.ptr(self.anc), H.ptr(pos),
-                                                       H.ptr(c), qkv.shape[0], self.ks[i].shape[1], h, d // h, C.c_float(1.0 / math.sqrt(d // h)),
-                                                       H.stream()), 'decode_attention_qkv')
-            else:
-                q = qkv[:, :d].contiguous().view(-1, 1, d)
-                self.ks[i].index_copy_(1, pos, qkv[:, d:2 * d].unsqueeze(1))
-                self.vs[i].index_copy_(1, pos, qkv[:, 2 * d:].unsqueeze(1))
-                if self.anc is not None:         # positions <= pos only: the kernel reads the step index from the device
-                    c = _attend1(q, self.ks[i], self.vs[i], h, None, rowmap=self.anc, last_pos=pos)
-                else:
-                    c = _attend1(q, self.ks[i], self.vs[i], h, kmask)
-            x = sa.linears[3](c.view(-1, d), resid=x)
-            ca, ff = layer.src_attn, layer.feed_forward
-            if fuse_ln:
-                q = fw.cln_linear(3 * i + 1, x, deltas, ops.shadow(ca.linears[0].weight), ca.linears[0].bias, d)
-            else:
-                q = ca.linears[0](fw.norm(3 * i + 1, x, deltas))
-            c = _attend1(q.view(-1, 1, d), self.kc[i], self.vc[i], h, self.src_mask)
-            x = ca.linears[3](c.view(-1, d), resid=x)
-            if fuse_ln:
-                hid = fw.cln_linear(3 * i + 2, x, deltas, ops.shadow(ff.w_1.weight), ff.w_1.bias, ff.w_1.weight.shape[0], act=H.ACT_RELU)
-                x = ff.w_2(hid, resid=x)
-            else:
-                x = ff(fw.norm(3 * i + 2, x, deltas), resid=x)
-        fn, lg = model.decoder.norm, self.dec.logit
-        V1 = lg.weight.shape[0]
-        if ln_ok and _FUSED_LN[0] in ('all', 'final'):
-            logits = fw.ln_linear(x, fn.gamma, fn.beta, fn.eps, ops.shadow(lg.weight, pad_rows=(V1 % 8 != 0)), lg.bias, V1, out_f32=True)
         else:
-            # straight into a persistent f32 buffer whose pad columns were zeroed once (no per-step fill)
-            Np = (V1 + 7) // 8 * 8
-            if getattr(self, 'logits_buf', None) is None or self.logits_buf.shape[0] != x.shape[0]:
-                self.logits_buf = torch.zeros(x.shape[0], Np, dtype=F32, device=x.device)
-            nf = n_final if n_final is not None else fn(x).view(-1, d)
-            ops.gemm(nf, ops.shadow(lg.weight, pad_rows=(V1 != Np)), self.logits_buf, x.shape[0], V1, d, lda=d, ldb=d, ldc=Np, bias=lg.bias)
-            logits = self.logits_buf
-        return ops.log_softmax(logits.view(logits.shape[0], -1), self.dec.vocab_size + 1, out=out, scale=self.logit_scale)
+            # one launch per projection, norm and attention (the only route for d_model or d_ff other than 512)
+            for i, layer in enumerate(model.decoder.layers):
+                c = self._self_attend(i, fw.qkv(i, fw.norm(3 * i, x, deltas).view(-1, d)), pos)
+                x = layer.self_attn.linears[3](c.view(-1, d), resid=x)
+                ca = layer.src_attn
+                q = ca.linears[0](fw.norm(3 * i + 1, x, deltas))
+                c = _attend1(q.view(-1, 1, d), self.kc[i], self.vc[i], h, self.src_mask)
+                x = ca.linears[3](c.view(-1, d), resid=x)
+                x = layer.feed_forward(fw.norm(3 * i + 2, x, deltas), resid=x)
+            n = model.decoder.norm(x).view(-1, d)
+        # the logits go straight into a persistent f32 buffer whose pad columns were zeroed once (no per-step fill)
+        lg = self.dec.logit
+        V1 = lg.weight.shape[0]
+        Np = (V1 + 7) // 8 * 8
+        if getattr(self, 'logits_buf', None) is None or self.logits_buf.shape[0] != x.shape[0]:
+            self.logits_buf = torch.zeros(x.shape[0], Np, dtype=F32, device=x.device)
+        ops.gemm(n, ops.shadow(lg.weight, pad_rows=(V1 != Np)), self.logits_buf, x.shape[0], V1, d, lda=d, ldb=d, ldc=Np, bias=lg.bias)
+        return ops.log_softmax(self.logits_buf, self.dec.vocab_size + 1, out=out, scale=self.logit_scale)
 
     def step(self, it):
         """it (R,) token ids at position self.t -> f32 log-probs (R, V+1) of the next token."""
@@ -560,24 +486,33 @@ class _Session:
         fused = _fused_weights(model)
         if self.st is None or self.fused_key is not fused:
             # (re)build the R-row state around the session's buffers; derived weights changed -> the captured step is stale as well
-            self.st = _DecoderState(dec, enc, src_mask, self.max_len, cross_kv=(self.kc, self.vc), rows=self.R)
+            self.st = _DecoderState(dec, enc, src_mask, self.max_len, cross_kv=(self.kc, self.vc), rows=self.R, row_table=True)
             self.fused_key = fused
-            if self.plan is not None:
-                _PLANS.append((self.plan, self.graph, torch.cuda.Event()))
-                _PLANS[-1][2].record()
-            self.graph = self.plan = None
+            self._retire_plan()
         self.st.enc, self.st.src_mask = enc, src_mask
         return src_mask
+
+    def _retire_plan(self):
+        """the captured step is stale (its weights changed): its plan is destroyed once the GPU has passed the replays issued so far"""
+        if self.plan is not None:
+            ev = torch.cuda.Event()
+            ev.record()
+            with _plans_lock:
+                _PLANS.append((self.plan, self.graph, ev))
+        self.graph = self.plan = None
 
     def _drive(self, n_body, first, step_hook, burst, extra=(), stop=None):
         """the token loop: n_body times _body(), body number i writing the log-probabilities of position i + first (step_hook(position,
         logp_buf, *extra) is called right after it).  On first use two bodies run as warm-up, the third is captured and turned into a
-        replay plan; the loop then replays.  A generator: yields after every issued step (see _run_iter of the subclasses).
+        replay plan; the loop then replays.  With _GRAPH_ENABLED off every body is issued eagerly instead: nothing is captured, and a
+        captured step the session holds is kept but not replayed.  A generator: yields after every issued step (see _run_iter of the
+        subclasses).
         stop(i) (optional, host only): asked before body number i (or the burst that starts with it) is issued; True ends the loop there."""
         dev = self.logp_buf.device
         done = 0
         cur = torch.cuda.current_stream()
-        if self.graph is None and n_body > 3 and _GRAPH_ENABLED[0]:
+        graph_on = _GRAPH_ENABLED[0]
+        if self.graph is None and n_body > 3 and graph_on:
             hook = step_hook if step_hook is not None else (lambda *a: None)
             side = _capture_stream(dev, ('warm', self.slot))
             side.wait_stream(cur)
@@ -607,14 +542,12 @@ class _Session:
                 cur.wait_stream(cap)
                 self.graph = graph
             except Exception as e:                                   # stay on the HIP path, just without the graph
-                import warnings
                 warnings.warn('decode: HIP graph capture failed (%s); running the steps eagerly' % e)
                 self.graph = None
             if self.graph is not None and _REPLAYER[0]:
                 # the library's own replayer (csrc/replay.hip): plain launches, ~3 us of host time per node (hipGraphLaunch: 7-12 us)
                 plan = H.lib.evk_replay_build(C.c_void_p(self.graph.raw_cuda_graph()), 16)
                 if not plan:
-                    import warnings
                     warnings.warn('decode: replay plan refused (%s); using hipGraphLaunch' % H.lib.evk_last_error().decode())
                     if hasattr(self.graph, 'instantiate'):
                         self.graph.instantiate()
@@ -624,7 +557,8 @@ class _Session:
                     H.check(H.lib.evk_replay_info(self.plan, info), 'replay_info')
                     self.step_launches = int(info[1])                 # kernel nodes of ONE captured token step
         stats['step_launches'] = getattr(self, 'step_launches', None)
-        bursts = burst > 0 and self.plan is not None and step_hook is None
+        graph, plan = (self.graph, self.plan) if graph_on else (None, None)
+        bursts = burst > 0 and plan is not None and step_hook is None
         if bursts:
             yield -1
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -635,17 +569,17 @@ class _Session:
                 n_body = it_
                 break
             n = min(int(burst), n_body - it_)
-            H.check(H.lib.evk_replay_run_n(self.plan, H.stream(), n), 'replay_run_n')
+            H.check(H.lib.evk_replay_run_n(plan, H.stream(), n), 'replay_run_n')
             it_ += n
             yield it_ - 1
         for it_ in range(it_, n_body):
             if stop is not None and stop(it_):
                 n_body = it_
                 break
-            if self.plan is not None:
-                H.check(H.lib.evk_replay_run(self.plan, H.stream()), 'replay_run')
-            elif self.graph is not None:
-                self.graph.replay()
+            if plan is not None:
+                H.check(H.lib.evk_replay_run(plan, H.stream()), 'replay_run')
+            elif graph is not None:
+                graph.replay()
             else:
                 self._body()
             if step_hook is not None:
@@ -654,8 +588,8 @@ class _Session:
         ev1.record()
         stats['step_events'] = (ev0, ev1, max(0, n_body - done))      # per-token step time = elapsed / count (bench.py)
         self.issued = max(n_body, done)                                  # bodies issued, warm-up included
-        stats['graph'] = self.graph is not None
-        stats['replayer'] = self.plan is not None
+        stats['graph'] = graph is not None
+        stats['replayer'] = plan is not None
         stats['fused_bookkeeping'] = True
 
 
@@ -688,7 +622,6 @@ def beam_options(args, beam, return_logprobs=False):
         raise NotImplementedError("diverse beam search (group_size > 1) is not on the path: the reference's own grouped search fails "
                                   '(CaptionModel.beam_search calls self.repeat_tensor, which no class defines), so there is nothing to match')
     if args.get('suppress_UNK', 0) and 'suppress_UNK' not in _warned:
-        import warnings
         _warned.add('suppress_UNK')
         warnings.warn("suppress_UNK is inert: the reference applies it only when the model has a `vocab` attribute, which EncoderDecoder "
                       'never has (caption_model.py:152); it has no effect here either')
@@ -767,6 +700,34 @@ def _beam_first_position(dec, logp0, beam, B, max_len, beam_sum, beam_seq, best_
     _beam_step(dec, lp0, beam, B, max_len, pos0, max_len == 1, beam_sum, beam_seq, best_p, best_seq, words, None, 0, None, None, None, None, lists)
 
 
+def _beam_book(dec, logp, t, base, beam_seq, beam_sum, best_p, best_seq):
+    """beam bookkeeping of position t in torch (caption_model.py beam_step + the finished-beam tracking), in place on the search's arrays:
+    logp holds one row per live hypothesis -- ONE per sample at t = 0, where the hypothesis count grows from B to B * beam and the running
+    sums are zero, `beam` per sample later -> (word_ix (B, beam), state_ix (B * beam,): the row each new hypothesis continues)."""
+    B, beam, max_len = beam_seq.shape
+    V1 = dec.vocab_size + 1
+    nb = 1 if t == 0 else beam
+    cand = logp.view(B, nb, -1)[:, :, :V1]
+    if t > 0:
+        cand = beam_sum.unsqueeze(-1) + cand
+    ys, ix = _topk(cand.reshape(B, nb * V1).contiguous(), beam)
+    beam_ix, word_ix = ix // V1, ix % V1
+    if t > 0:
+        beam_seq.copy_(beam_seq.gather(1, beam_ix.unsqueeze(-1).expand(-1, -1, max_len)))
+    beam_seq[:, :, t] = word_ix
+    beam_sum.copy_(ys)
+    is_end = torch.ones_like(word_ix, dtype=torch.bool) if t == max_len - 1 else (word_ix == dec.eos_idx)
+    # finished beams: keep, per sample, the best p seen so far (earlier / lower beam index wins ties)
+    p_end = torch.where(is_end, beam_sum, torch.full_like(beam_sum, -float('inf')))
+    pv, pi = p_end.max(dim=1)
+    better = pv > best_p
+    cand_seq = beam_seq.gather(1, pi.view(B, 1, 1).expand(-1, 1, max_len))[:, 0]
+    best_seq.copy_(torch.where(better.unsqueeze(1), cand_seq, best_seq))
+    best_p.copy_(torch.where(better, pv, best_p))
+    beam_sum.sub_(1000.0 * is_end.to(F32))
+    return word_ix, (beam_ix + base * nb).reshape(-1)
+
+
 class _BeamSession(_Session):
     """The session of a beam search over B samples x `beam` hypotheses: the shared state plus the beam bookkeeping arrays."""
 
@@ -791,28 +752,7 @@ class _BeamSession(_Session):
     def _body(self):
         """positions 1 .. max_len-2: bookkeeping at position `pos` (which also advances it), then the decoder step that writes pos + 1"""
         self._book_kernel(False)
-        self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
-
-    def _first_position(self, logp0, hook):
-        """position 0 of the plain search, eagerly in torch (the hypothesis count grows from B to B * beam here) -> (word_ix, state_ix)"""
-        dec, B, beam, max_len = self.dec, self.B, self.beam, self.max_len
-        V1 = dec.vocab_size + 1
-        hook(0, logp0, self.beam_sum)
-        ys, ix = _topk(logp0.view(B, -1)[:, :V1].contiguous(), beam)
-        word_ix = ix % V1                                                   # one source hypothesis per sample: the flat index IS the word
-        state_ix = self.base.expand(B, beam).reshape(-1)                    # hypothesis r of sample b starts from sample b's state
-        self.beam_seq[:, :, 0] = word_ix
-        self.beam_sum.copy_(ys)
-        last = max_len == 1
-        is_end = torch.ones_like(word_ix, dtype=torch.bool) if last else (word_ix == dec.eos_idx)
-        p_end = torch.where(is_end, self.beam_sum, torch.full_like(self.beam_sum, -float('inf')))
-        pv, pi = p_end.max(dim=1)
-        better = pv > self.best_p
-        cand_seq = self.beam_seq.gather(1, pi.view(B, 1, 1).expand(-1, 1, max_len))[:, 0]
-        self.best_seq.copy_(torch.where(better.unsqueeze(1), cand_seq, self.best_seq))
-        self.best_p.copy_(torch.where(better, pv, self.best_p))
-        self.beam_sum.sub_(1000.0 * is_end.to(F32))
-        return word_ix, state_ix
+        self.st.step_static(self.words, self.pos, out=self.logp_buf, seed_rows=False)
 
     def _run_iter(self, enc, src_mask, return_scores=False, step_hook=None, burst=0):
         """run() as a generator that yields after every issued token step: a scheduler that drives several sessions (one per HIP stream)
@@ -844,7 +784,8 @@ class _BeamSession(_Session):
             word_ix = self.words.view(B, beam).clone()
             state_ix = self.base.expand(B, beam).reshape(-1)
         else:
-            word_ix, state_ix = self._first_position(logp0, hook)
+            hook(0, logp0, self.beam_sum)
+            word_ix, state_ix = _beam_book(dec, logp0, 0, self.base, self.beam_seq, self.beam_sum, self.best_p, self.best_seq)
         if max_len > 1:
             # the B -> B*beam expansion: every hypothesis inherits its sample's memory and position-0 keys / values
             ops.copy_kernel(st.mem, st0.mem.index_select(0, state_ix).contiguous())
@@ -859,12 +800,9 @@ class _BeamSession(_Session):
                 st.vs[i][:, :1] = st0.vs[i][:, :1].index_select(0, state_ix)
             self.pos.fill_(1)
             self.ticket.zero_()
-            if st.anc is not None:
-                st.anc.copy_(st.rows.expand_as(st.anc))
+            st.anc.copy_(st.rows.expand_as(st.anc))
             self.words.copy_(word_ix.reshape(-1))
-            st.step_static(self.words, self.pos, None, out=self.logp_buf)       # writes position 1 (and builds the row table on first use)
-            if st.anc is None:
-                raise RuntimeError('beam session needs the cache row table (head dim 64, max_seq_len <= 256)')
+            st.step_static(self.words, self.pos, out=self.logp_buf)             # writes position 1
             hook(1, self.logp_buf, self.beam_sum)
             # positions 1 .. max_len-2: body number i writes the log-probabilities of position i + 2
             yield from self._drive(max_len - 2, 2, step_hook, burst, (self.beam_sum,))
@@ -902,7 +840,7 @@ class _SampleSession(_Session):
     def _body(self):
         """the choice at position `pos` (which also advances it), then the decoder step that reads the chosen words at pos + 1"""
         self._book_kernel(False)
-        self.st.step_static(self.words, self.pos, None, out=self.logp_buf, seed_rows=False)
+        self.st.step_static(self.words, self.pos, out=self.logp_buf, seed_rows=False)
 
     def _run_iter(self, enc, src_mask, uniforms=None, step_hook=None, burst=0):
         """as _BeamSession._run_iter (same yields, same burst protocol) -> (seq, seq_logprobs or None)"""
@@ -930,9 +868,7 @@ class _SampleSession(_Session):
         self.pos.zero_()
         self.ticket.zero_()
         self.words.fill_(dec.bos_idx)
-        st.step_static(self.words, self.pos, None, out=self.logp_buf)        # position 0 (and builds the row table on first use: the identity)
-        if st.anc is None:
-            raise RuntimeError('sample session needs the cache row table (head dim 64, max_seq_len <= 256)')
+        st.step_static(self.words, self.pos, out=self.logp_buf)              # position 0 (the row table stays the identity it was built as)
         hook(0, self.logp_buf)
         # positions 0 .. max_len-2: body number i chooses the word of position i and writes the log-probabilities of position i + 1
         yield from self._drive(max_len - 1, 1, step_hook, burst)
@@ -949,16 +885,28 @@ def _sample_step(dec, logp, pos, seq, unfinished, words, seq_logprobs, uniforms,
                                   H.ptr(pos_advance), H.ptr(ticket), H.stream()), 'sample_step')
 
 
-import weakref  # noqa: E402
-
-_SESSIONS = weakref.WeakKeyDictionary()          # decoder module -> {geometry: _BeamSession}
+_SESSIONS = weakref.WeakKeyDictionary()          # decoder module -> {key: session}, the most recently used last
 
 
-def _session_ok(dec, args, enc):
+def _session_ok(dec, args):
+    """the session serves this geometry (its kernels read the self-attention caches through the row table: head dim 64, <= 256 positions)"""
     model = dec.model
     h = model.decoder.layers[0].self_attn.h
-    return (_INDIRECT[0] and _FUSED_BOOK[0] and _FUSED_APPEND[0] and _GRAPH_ENABLED[0] and model.d_model // h == 64 and
-            int(args['max_seq_len']) <= 256 and tunable('EVK_DECODE_SESSION', '1') != '0')
+    return _SESSION[0] and model.d_model // h == 64 and int(args['max_seq_len']) <= 256
+
+
+def _session_for(dec, key, make):
+    """the decoder's session under `key`, built by make() on first use.  A few batch geometries / slots at most (each holds its caches:
+    6 x R x max_len x 512 x 2 B), the least recently used evicted first.  A generator still in flight keeps its evicted session alive, whose
+    plan is then destroyed behind a device synchronisation: keep EVK_DECODE_DEPTH times the batch geometries in use at 6 or below."""
+    sessions = _SESSIONS.setdefault(dec, {})
+    ses = sessions.pop(key, None)
+    if ses is None:
+        ses = make()
+        while len(sessions) >= 6:
+            sessions.pop(next(iter(sessions)))
+    sessions[key] = ses
+    return ses
 
 
 @torch.no_grad()
@@ -979,25 +927,20 @@ def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=
     opts = beam_options(args, beam, return_logprobs)
     if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
         raise ValueError('beam_size must be in [1, 8]')
-    if not _session_ok(dec, args, enc_states):
-        if as_iterator:
-            raise NotImplementedError('stepwise beam search needs the session path')
-        return _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores, step_hook, return_logprobs)
+    session = _session_ok(dec, args)
+    if as_iterator and not session:
+        raise NotImplementedError('stepwise beam search needs the session path')
     was_training = dec.training
     dec.eval()
     try:
         enc, src_mask = dec.encode(enc_states, enc_mask)
+        if not session:
+            return _beam_eager(dec, enc, src_mask, beam, max_len, opts, return_scores, step_hook)
         B, S, dev = enc.shape[0], enc.shape[1], enc.device
         key = (B, beam, max_len, S, dev.index, src_mask is None, slot)
         if opts is not None:
             key = key + (tuple(sorted(opts.items())),)
-        sessions = _SESSIONS.setdefault(dec, {})
-        ses = sessions.pop(key, None)
-        if ses is None:
-            ses = _BeamSession(dec, B, beam, max_len, S, dev, slot, opts)
-            while len(sessions) >= 6:                   # a few batch geometries / slots at most (each holds its caches: 6 x R x max_len x 512 x 2 B)
-                sessions.pop(next(iter(sessions)))
-        sessions[key] = ses
+        ses = _session_for(dec, key, lambda: _BeamSession(dec, B, beam, max_len, S, dev, slot, opts))
         if as_iterator:
             return ses.run_iter(enc, src_mask, return_scores, step_hook, burst)
         return ses.run(enc, src_mask, return_scores, step_hook)
@@ -1062,19 +1005,13 @@ def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=Non
             if tuple(uniforms.shape) != (R, max_len):
                 raise ValueError('uniforms must be (%d, %d)' % (R, max_len))
             uniforms = uniforms.to(device=dev, dtype=F32)
-        if not _session_ok(dec, args, enc_states):
+        if not _session_ok(dec, args):
             if as_iterator:
                 raise NotImplementedError('stepwise sampling needs the session path')
             return _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_hook, uniforms)
         # ('sample' in front: a beam session's key starts with an integer)
         key = ('sample', B, n, max_len, S, dev.index, src_mask is None, slot, bool(return_logprobs), tuple(sorted(opts.items())))
-        sessions = _SESSIONS.setdefault(dec, {})
-        ses = sessions.pop(key, None)
-        if ses is None:
-            ses = _SampleSession(dec, B, n, max_len, S, dev, opts, return_logprobs, slot)
-            while len(sessions) >= 6:
-                sessions.pop(next(iter(sessions)))
-        sessions[key] = ses
+        ses = _session_for(dec, key, lambda: _SampleSession(dec, B, n, max_len, S, dev, opts, return_logprobs, slot))
         if as_iterator:
             return ses.run_iter(enc, src_mask, uniforms, step_hook, burst)
         return ses.run(enc, src_mask, uniforms, step_hook)
@@ -1083,17 +1020,14 @@ def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=Non
 
 
 def _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_hook, uniforms):
-    """sample() without the persistent session (head dims other than 64, max_seq_len > 256, or the debugging switches): the decoder steps
+    """sample() without the persistent session (head dims other than 64, max_seq_len > 256, or EVK_DECODE_SESSION=0): the decoder steps
     run eagerly with the position on the host; the choice is the same kernel."""
     B, dev, V1 = enc.shape[0], enc.device, dec.vocab_size + 1
     R = B * n
     cross = ([l.src_attn.linears[1](enc) for l in dec.model.decoder.layers], [l.src_attn.linears[2](enc) for l in dec.model.decoder.layers])
     st = _DecoderState(dec, enc, src_mask, max_len, cross_kv=cross, rows=R)
     if n > 1:
-        # (the eager step's attention wants one K / V row per query row)
-        st.kc = [k.repeat_interleave(n, 0) for k in st.kc]
-        st.vc = [v.repeat_interleave(n, 0) for v in st.vc]
-        st.src_mask = src_mask.repeat_interleave(n, 0) if src_mask is not None else None
+        st.expand_cross(n)
     seq = torch.full((R, max_len), dec.pad_idx, dtype=torch.long, device=dev)
     unfinished = torch.ones(R, dtype=torch.uint8, device=dev)
     words = torch.full((R,), dec.bos_idx, dtype=torch.long, device=dev)
@@ -1108,185 +1042,35 @@ def _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_ho
     return seq, seq_logprobs
 
 
-@torch.no_grad()
-def _beam_search_legacy(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, return_logprobs=False):
-    """beam_search without the persistent session (head dims other than 64, max_seq_len > 256, or the debugging switches): every call
-    allocates its state and captures its own graph.  The options (beam_options) run through the same kernel as on the session path, which
-    needs the cache row table: without it (max_seq_len > 256, head dims other than 64) a search with options is refused."""
-    was_training = dec.training
-    dec.eval()
-    try:
-        beam, max_len = int(args.get('beam_size', 3)), int(args['max_seq_len'])
-        opts = beam_options(args, beam, return_logprobs)
-        if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
-            raise ValueError('beam_size must be in [1, 8]')
-        enc, src_mask = dec.encode(enc_states, enc_mask)
-        B, dev = enc.shape[0], enc.device
-        V1 = dec.vocab_size + 1
-        lists = _BeamLists(dec, B, beam, max_len, dev, opts) if opts is not None else None
-        st = _DecoderState(dec, enc, src_mask, max_len)
-        logp = st.step(torch.full((B,), dec.bos_idx, dtype=torch.long, device=dev))            # (B, V+1)
-        base = torch.arange(B, device=dev).unsqueeze(1)
-        beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
-        beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
-        best_p = torch.full((B,), -float('inf'), dtype=F32, device=dev)
-        best_seq = torch.full((B, max_len), dec.pad_idx, dtype=torch.long, device=dev)
-        def book(t_host, last):
-            """beam bookkeeping of one step (caption_model.py beam_step + the finished-beam tracking) on persistent buffers;
-            t_host None -> the position comes from the device tensor `pos` (graph mode)."""
-            nonlocal beam_seq, beam_sum, best_p, best_seq, nb
-            cand = (beam_sum[:, :nb].unsqueeze(-1) + logp[0].view(B, nb, V1)).reshape(B, nb * V1).contiguous()
-            ys, ix = _topk(cand, beam)
-            beam_ix, word_ix = ix // V1, ix % V1
-            state_ix = (beam_ix + base * nb).reshape(-1)
-            if t_host is None:
-                beam_seq.copy_(beam_seq.gather(1, beam_ix.unsqueeze(-1).expand(-1, -1, max_len)))
-                beam_seq.index_copy_(2, pos, word_ix.unsqueeze(-1))
-                st.reorder_static(state_ix)
-            else:
-                if t_host > 0:
-                    beam_seq = beam_seq.gather(1, beam_ix.unsqueeze(-1).expand(-1, -1, max_len))
-                beam_seq[:, :, t_host] = word_ix
-                st.reorder(state_ix)
-            beam_sum.copy_(ys)
-            is_end = torch.ones_like(word_ix, dtype=torch.bool) if last else (word_ix == dec.eos_idx)
-            # finished beams: keep, per sample, the best p seen so far (earlier / lower beam index wins ties)
-            p_end = torch.where(is_end, beam_sum, torch.full_like(beam_sum, -float('inf')))
-            pv, pi = p_end.max(dim=1)
-            better = pv > best_p
-            cand_seq = beam_seq.gather(1, pi.view(B, 1, 1).expand(-1, 1, max_len))[:, 0]
-            best_seq.copy_(torch.where(better.unsqueeze(1), cand_seq, best_seq))
-            best_p.copy_(torch.where(better, pv, best_p))
-            beam_sum.sub_(1000.0 * is_end.to(F32))
-            return word_ix
-
-        words = torch.empty(B * beam, dtype=torch.long, device=dev)
-
-        ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def book_kernel(last):
-            """book(None, last) as ONE launch (csrc/beam.hip): top-beam, sequence / cache-row-table / relational-memory reorder in
-            place, finished-beam tracking, -1000 penalty, next input tokens -- and, between steps, the position counter's increment and
-            the row-table column of the next position."""
-            _beam_step(dec, logp[0], beam, B, max_len, pos, last, beam_sum, beam_seq, best_p, best_seq, words,
-                       st.mem32 if st.mem32 is not None else st.mem, st.mem[0].numel() * (2 if st.mem32 is not None else 1), st.anc,
-                       None if last else pos, ticket, None, lists)
-            return words
-
-        nb = 1
-        logp = [logp]
-        hook = step_hook if step_hook is not None else (lambda *a: None)
-        # t = 0 (the hypothesis count grows from B to B*beam here) runs eagerly
-        if lists is not None:
-            lists.reset()
-            beam_sum.fill_(-float('inf'))
-            beam_sum[:, 0] = 0.0
-            hook(0, logp[0], beam_sum)
-            _beam_first_position(dec, logp[0], beam, B, max_len, beam_sum, beam_seq, best_p, best_seq, words, lists)
-            w = words.view(B, beam).clone()
-            if max_len > 1:
-                st.reorder(base.expand(B, beam).reshape(-1))           # every hypothesis starts from its study's state
-                st.logit_scale = 1.0 / opts['temperature']             # positions >= 1 only (att_model.py:119)
-        else:
-            hook(0, logp[0], beam_sum)
-            w = book(0, max_len == 1)
-        if max_len > 1:
-            nb = beam
-            R = B * beam
-            pos = torch.ones(1, dtype=torch.long, device=dev)            # device-side step index t
-            ar = torch.arange(max_len, device=dev).unsqueeze(0)
-            logp_buf = st.step_static(w.reshape(-1), pos, (ar <= pos).expand(R, -1).to(torch.uint8).contiguous()).clone()
-            logp[0] = logp_buf
-            hook(1, logp_buf, beam_sum)
-
-            fused_book = _FUSED_BOOK[0] and st.anc is not None and beam_seq.is_contiguous() and st.mem.is_contiguous()
-            stats['fused_bookkeeping'] = bool(fused_book)
-            if lists is not None and not fused_book:
-                raise NotImplementedError('beam search options (temperature, decoding_constraint, length_penalty, sample_n, log-probabilities) '
-                                          'need the fused bookkeeping kernel and the cache row table (head dim 64, max_seq_len <= 256)')
-
-            def body():
-                """steps 1 .. max_len-2: bookkeeping at position `pos`, then the decoder step that writes position pos+1."""
-                if fused_book:
-                    w_ = book_kernel(False)              # (advances pos and seeds the row table's next column itself)
-                else:
-                    w_ = book(None, False)
-                    pos.add_(1)
-                kmask = (ar <= pos).expand(R, -1).to(torch.uint8).contiguous() if st.anc is None else None
-                st.step_static(w_.reshape(-1), pos, kmask, out=logp_buf, seed_rows=not fused_book)
-
-            n_body = max_len - 2                                         # iterations t = 1 .. max_len-2
-            graph = plan = None
-            done = 0
-            if n_body > 3 and _GRAPH_ENABLED[0]:
-                cur = torch.cuda.current_stream()
-                side = _capture_stream(dev, 'warm')
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):                           # warm-up iterations (real steps) off the default stream
-                    body()
-                    hook(2, logp_buf, beam_sum)
-                    body()
-                    hook(3, logp_buf, beam_sum)
-                cur.wait_stream(side)
-                done = 2
-                try:
-                    # captured by hand (capture_begin / capture_end on a side stream) rather than through torch.cuda.graph(): the context
-                    # manager opens with a DEVICE-WIDE synchronize, which would make this decode wait for the next batch's encoders that
-                    # FineTune.generate_pipelined has just queued on another stream
-                    graph = torch.cuda.CUDAGraph(keep_graph=_REPLAYER[0])
-                    cap = _capture_stream(dev)
-                    pool = _graph_pool(dev)
-                    cap.wait_stream(cur)
-                    with torch.cuda.stream(cap):
-                        graph.capture_begin(pool=pool)
-                        try:
-                            body()
-                        finally:
-                            graph.capture_end()
-                    cur.wait_stream(cap)
-                except Exception as e:                                   # stay on the HIP path, just without the graph
-                    import warnings
-                    warnings.warn('decode: HIP graph capture failed (%s); running the steps eagerly' % e)
-                    graph = None
-                if graph is not None and _REPLAYER[0]:
-                    # hipGraphLaunch costs 7-12 us of HOST time per node on ROCm 7.2 -- ~0.45 ms for this ~60-kernel step, exactly the
-                    # step time that was measured: the replays were host-bound.  The library's own replayer (csrc/replay.hip) walks the
-                    # captured graph once and re-issues it with plain launches (~3 us per node).
-                    plan = H.lib.evk_replay_build(C.c_void_p(graph.raw_cuda_graph()), 16)
-                    if not plan:
-                        import warnings
-                        warnings.warn('decode: replay plan refused (%s); using hipGraphLaunch' % H.lib.evk_last_error().decode())
-                        graph.instantiate() if hasattr(graph, 'instantiate') else None
-                    plan = plan or None
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+def _beam_eager(dec, enc, src_mask, beam, max_len, opts, return_scores, step_hook):
+    """beam_search() without the persistent session (head dims other than 64, max_seq_len > 256, or EVK_DECODE_SESSION=0): the decoder
+    steps run eagerly with the position on the host, the bookkeeping in torch, and the self-attention caches themselves are re-ordered.
+    The options (beam_options) are arguments of the session's bookkeeping kernel and are refused here."""
+    if opts is not None:
+        raise NotImplementedError('beam search options (temperature, decoding_constraint, length_penalty, sample_n, log-probabilities) '
+                                  'need the fused bookkeeping kernel and the cache row table (head dim 64, max_seq_len <= 256)')
+    B, dev = enc.shape[0], enc.device
+    st = _DecoderState(dec, enc, src_mask, max_len)
+    base = torch.arange(B, device=dev).unsqueeze(1)
+    beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
+    beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
+    best_p = torch.full((B,), -float('inf'), dtype=F32, device=dev)
+    best_seq = torch.full((B, max_len), dec.pad_idx, dtype=torch.long, device=dev)
+    words = torch.full((B,), dec.bos_idx, dtype=torch.long, device=dev)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for t in range(max_len):
+        logp = st.step(words)
+        if step_hook is not None:
+            step_hook(t, logp, beam_sum)
+        word_ix, state_ix = _beam_book(dec, logp, t, base, beam_seq, beam_sum, best_p, best_seq)
+        words = word_ix.reshape(-1)
+        if t + 1 < max_len:
+            st.reorder(state_ix)
+        if t == 0:
+            st.expand_cross(beam)
             ev0.record()
-            for it_ in range(done, n_body):
-                if plan is not None:
-                    H.check(H.lib.evk_replay_run(plan, H.stream()), 'replay_run')
-                elif graph is not None:
-                    graph.replay()
-                else:
-                    body()
-                if step_hook is not None:
-                    step_hook(it_ + 2, logp_buf, beam_sum)       # body number it_ wrote the log-probabilities of position it_ + 2
-            ev1.record()
-            stats['step_events'] = (ev0, ev1, max(0, n_body - done))      # per-token step time = elapsed / count (bench.py)
-            stats['graph'] = graph is not None
-            stats['replayer'] = plan is not None
-            if graph is not None:
-                _last_graph[torch.device(dev).index] = graph
-            if plan is not None:
-                _PLANS.append((plan, graph, torch.cuda.Event()))
-                _PLANS[-1][2].record()
-                _reap_plans()
-            if fused_book:
-                book_kernel(True)                                        # t = max_len - 1: every live beam is closed
-            else:
-                book(None, True)
-        if lists is not None:
-            return lists.result(return_scores)
-        if return_scores:
-            return best_seq, best_p
-        return best_seq
-    finally:
-        dec.train(was_training)
+    ev1.record()
+    stats.update(step_events=(ev0, ev1, max_len - 1), step_launches=None, graph=False, replayer=False, fused_bookkeeping=False)
+    if return_scores:
+        return best_seq, best_p
+    return best_seq

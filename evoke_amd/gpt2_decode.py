@@ -128,11 +128,7 @@ class _GPT2Session(decode._Session):
         ps = list(dec.parameters())
         key = (ops.WEIGHT_EPOCH[0], tuple(p._version for p in ps), ps[0].data_ptr())
         if key != self.weights_key:
-            if self.plan is not None:
-                with decode._plans_lock:
-                    decode._PLANS.append((self.plan, self.graph, torch.cuda.Event()))
-                    decode._PLANS[-1][2].record()
-            self.graph = self.plan = None
+            self._retire_plan()
             self.weights_key = key
         self.seqs.fill_(dec.pad_token_id)
         self.seqs[:, 0] = dec.bos_token_id
@@ -204,16 +200,7 @@ def search(dec, enc, n_return, return_scores=False, step_hook=None, slot=0, as_i
     B, S, dev = enc.shape[0], enc.shape[1], enc.device
     nb, max_len = int(dec.beam_size), int(dec.max_seq_len)
     key = ('gpt2', B, nb, max_len, S, dev.index, slot, n_return)
-    sessions = decode._SESSIONS.setdefault(dec, {})
-    ses = sessions.pop(key, None)
-    if ses is None:
-        ses = _GPT2Session(dec, B, nb, max_len, S, dev, slot, n_return)
-        # the cap and the eviction of decode.beam_search: a few geometries / slots at most, each holding its caches.  A generator still in
-        # flight keeps its evicted session alive, whose plan is then destroyed behind a device synchronisation: keep EVK_DECODE_DEPTH
-        # times the batch geometries in use at 6 or below
-        while len(sessions) >= 6:
-            sessions.pop(next(iter(sessions)))
-    sessions[key] = ses
+    ses = decode._session_for(dec, key, lambda: _GPT2Session(dec, B, nb, max_len, S, dev, slot, n_return))
     enc = enc.contiguous()
     if as_iterator:
         return ses.run_iter(enc, return_scores, step_hook, burst)

@@ -107,6 +107,15 @@ def test_host_validation_needs_no_device():
         decode.beam_options(dict(base, suppress_UNK=1), 4)
 
 
+def test_retired_decode_paths_are_gone():
+    """the legacy beam search, the switches that selected lost experiments and the key-mask form of the static step"""
+    import inspect
+    from evoke_amd import decode
+    for name in ('_beam_search_legacy', '_INDIRECT', '_FUSED_BOOK', '_FUSED_APPEND', '_FUSED_LN'):
+        assert not hasattr(decode, name), name
+    assert 'kmask' not in inspect.signature(decode._DecoderState.step_static).parameters
+
+
 @functools.lru_cache(maxsize=None)
 def model_restatement(oname):
     """the restatement over the oracle's decoder on case beam224_b4 under one option set of the model fixture"""

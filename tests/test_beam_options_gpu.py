@@ -317,20 +317,25 @@ def test_beam_options_end_to_end_on_the_reference_fixture(model, enc, oname):
 
 
 @pytest.mark.parametrize('oname', list(MODEL_OPTS) + ['avg_nbest'])
-def test_beam_options_session_path_equals_the_legacy_path(model, enc, oname):
+def test_beam_options_replayed_step_equals_the_eagerly_issued_step(model, enc, oname):
+    """the session replaying its captured step vs the SAME session issuing the same launches eagerly (_GRAPH_ENABLED off: the captured
+    step is kept, not replayed), and the same session replaying its kept step again afterwards"""
     from evoke_amd import decode
     args = _args(oname) if oname in MODEL_OPTS else _args('nbest', length_penalty='avg_0')
     x, enc_mask = enc
     seq, slp, p = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
     assert decode.stats.get('graph')
     saved = decode._GRAPH_ENABLED[0]
-    decode._GRAPH_ENABLED[0] = False                                              # no session: _beam_search_legacy, eager steps
+    decode._GRAPH_ENABLED[0] = False                                              # the same session, eager steps
     try:
         seq_l, slp_l, p_l = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
     finally:
         decode._GRAPH_ENABLED[0] = saved
     assert not decode.stats.get('graph')
     assert torch.equal(seq, seq_l) and torch.equal(p, p_l) and torch.equal(slp, slp_l)
+    seq_r, slp_r, p_r = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, return_logprobs=True)
+    assert decode.stats.get('graph')
+    assert torch.equal(seq, seq_r) and torch.equal(p, p_r) and torch.equal(slp, slp_r)
     seq_only = decode.beam_search(model.text_decoder, x, enc_mask, args)
     assert torch.equal(seq_only, seq)
     decode._SESSIONS.clear()

@@ -432,7 +432,28 @@ def test_beam_search_16bit_recurrence_stays_within_the_reference_16bit_drift():
         decode._SESSIONS.clear()
 
 
-def _beam100(decode, FineTune, S, name, rm_f32):
+def test_beam_search_host_loop_fallback_follows_the_reference_decisions():
+    """The host-loop fallback (decode._beam_eager: the route of head dims other than 64, max_seq_len > 256 and EVK_DECODE_SESSION=0) on
+    beam224_b4 (2 studies, beam 4, 14 positions), teacher-forced and free-running against the reference's trace as the session is in
+    test_beam_search_follows_the_reference_decisions, with the same flat LOGP_TOL.  Not asked of it: "own top set equals the reference at
+    all but two positions" -- a measured property of the session's arithmetic; in this golden 4 and 3 of the 14 positions have a
+    reference margin below 2 x LOGP_TOL, so the reference alone does not guarantee it.  Measured: largest teacher-forced error 3.4e-3
+    (the session on the same golden: 3.3e-3), own top-4 set equal at 14 / 14 positions."""
+    from evoke_amd import decode
+    from evoke_amd.model_pretrain_finetune import FineTune
+    from oracle import spec as S
+    assert decode._RM_F32[0]
+    saved = decode._SESSION[0]
+    decode._SESSION[0] = False
+    try:
+        _beam100(decode, FineTune, S, 'beam224_b4', True, session=False)
+    finally:
+        decode._SESSION[0] = saved
+        decode._SESSIONS.clear()
+
+
+def _beam100(decode, FineTune, S, name, rm_f32, session=True):
+    """session: the route the searches are expected to take -- the session's replayed step with the bookkeeping kernel, or the host loop"""
     case, gold, tr = CASES[name], _gold(name), _gold(name + '_trace')
     beam, T, B, V1 = case['beam_size'], case['max_seq_len'], case['B'], V + 1
     inp = make_inputs(case, V)
@@ -488,7 +509,7 @@ def _beam100(decode, FineTune, S, name, rm_f32):
     with torch.no_grad():
         x, enc_mask = model.encoder_states(inp['images'].cuda(), np.array(inp['patient_ids']), B, inp['inc_ids'], inp['inc_masks'])
         seq_forced, p_forced = decode.beam_search(model.text_decoder, x, enc_mask, args, return_scores=True, step_hook=forced)
-        assert decode.stats.get('graph') and decode.stats.get('fused_bookkeeping'), decode.stats
+        assert bool(decode.stats.get('graph')) == session and bool(decode.stats.get('fused_bookkeeping')) == session, decode.stats
         seq_free = decode.beam_search(model.text_decoder, x, enc_mask, args, step_hook=watch)
         seq_plain = decode.beam_search(model.text_decoder, x, enc_mask, args)
     err = torch.stack(rec['err']).numpy()                 # (T, B)
@@ -505,7 +526,7 @@ def _beam100(decode, FineTune, S, name, rm_f32):
     assert (err <= tol).all(), 'positions beyond the tolerance: %s' % np.argwhere(err > tol)[:10].tolist()
     bad = ~same & (margin > 2 * tol)
     assert not bad.any(), 'the engine selects another beam set where the reference margin is %s' % margin[bad]
-    if rm_f32 and F16:
+    if rm_f32 and F16 and session:
         assert (same.sum(0) >= T - 2).all(), same.sum(0)
     assert torch.equal(seq_forced.cpu(), want), 'forced search does not return the reference ids: bookkeeping / state re-order differ'
     np.testing.assert_allclose(p_forced.cpu().numpy(), tr['best_p'], atol=2e-2, rtol=0)

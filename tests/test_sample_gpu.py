@@ -186,16 +186,16 @@ def test_sample_stochastic_methods_smoke(model):
 
 
 def test_sample_eager_fallback_returns_the_same_report(model):
-    """geometries without a session (here: graph capture switched off) run the decoder steps eagerly around the same kernel"""
+    """geometries without a session (here: the session switched off) run the decoder steps eagerly around the same kernel"""
     from evoke_amd import decode
     g, args = load('sample224_n2'), _args('sample224_n2')
     x, enc_mask = _encoder_states(model, 'beam224')
-    saved = decode._GRAPH_ENABLED[0]
-    decode._GRAPH_ENABLED[0] = False
+    saved = decode._SESSION[0]
+    decode._SESSION[0] = False
     try:
         seq, slp = decode.sample(model.text_decoder, x, enc_mask, args, return_logprobs=True)
     finally:
-        decode._GRAPH_ENABLED[0] = saved
+        decode._SESSION[0] = saved
     seq = seq.cpu().numpy()
     for r, p in enumerate(_first_open(_pinned(g))):
         assert seq[r, :p].tolist() == g['seq'][r, :p].tolist(), r
