@@ -1,0 +1,262 @@
+// hf_sample.hip -- one kernel per generated token for everything Hugging Face's `generate` does between two decoder steps when it samples or
+// decodes greedily (num_beams 1): the standard logits processors in HF's order -- RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor,
+// MinLengthLogitsProcessor, then with do_sample TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper -- the choice of the next token and
+// the finished-row bookkeeping.  The distilgpt2 backend's counterpart of sample.hip, which restates the R2Gen reference's own rules
+// (log-probability input, trigram penalty, another nucleus definition) and cannot be borrowed: the processors act on the RAW f32 logits (the
+// repetition penalty depends on the sign), so this kernel reads the head's output directly and no log_softmax launch precedes it.
+// One workgroup owns one row; only the row (and the row's history) lives in LDS, softmax weights are recomputed where they are needed, so a
+// vocabulary of 12288 entries fits the 64 KB a workgroup may ask for without a device attribute.  Top-k and top-p both reduce to a VALUE
+// threshold -- entries strictly below the k-th largest value leave; an entry stays iff the probability mass of all entries <= its value exceeds
+// 1 - p -- found by the bisection over the order-preserving integer image of the floats that sample.hip uses; entries of equal value stay or
+// leave together, so no tie ordering exists.  The draw is an inverse CDF over the kept entries in vocabulary order with a uniform number the
+// caller supplies (no generator state in the kernel: a replayed graph reads a refilled buffer).
+#include <stdlib.h>
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;            // threads per workgroup (4 waves)
+constexpr int UNR = 8;             // row elements a thread requests before it uses the first one
+constexpr int V_MAX = 12288;       // one f32 row of V in LDS (48 KB)
+constexpr int LEN_MAX = 256;       // the row's history in LDS (1 KB)
+constexpr int NGRAM_MAX = 8;
+constexpr int NONE = 0x7fffffff;
+
+struct HfSampleP {
+  const float* logits; int ld;        // [R][ld] f32 raw logits of the step, V valid columns
+  int V, max_len, eos, pad, do_sample, ngram, min_length, top_k;
+  float rep_penalty, temperature, top_p;
+  const long long* pos;               // device scalar: last filled column of seqs (cur_len = *pos + 1 ids so far, [BOS] included)
+  long long* seqs;                    // [R][max_len] (in / out): the new id goes to column cur_len
+  unsigned char* unfinished;          // [R] (in / out; the caller sets 1 before the first step)
+  long long* words;                   // [R] out: tokens fed to the next decoder step
+  int* n_done;                        // *n_done += rows that finished in this launch
+  float* tok_logp;                    // [R][max_len] or null: log-probability of the chosen token under the processed row
+  float* rows_out;                    // [max_len][R][V] or null: the processed row
+  const float* uniforms;              // [R][max_len] or null (greedy)
+  long long* pos_out; int* ticket;    // advance: the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
+};
+
+// block-wide reductions: per-wave shuffle, then one LDS round; the result is returned to every thread
+__device__ __forceinline__ void block_argmax(float& v, int& i, float* s_val, int* s_idx) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  __syncthreads();                    // (the scratch words may still be read from an earlier round)
+  if (lane == 0) { s_val[wave] = v; s_idx[wave] = i; }
+  __syncthreads();
+  v = s_val[0]; i = s_idx[0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w) if (s_val[w] > v || (s_val[w] == v && s_idx[w] < i)) { v = s_val[w]; i = s_idx[w]; }
+}
+__device__ __forceinline__ float block_sum(float v, float* s_val) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) s_val[wave] = v;
+  __syncthreads();
+  v = s_val[0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w) v += s_val[w];
+  return v;
+}
+// order-preserving image of a float in the unsigned integers
+__device__ __forceinline__ uint32_t fkey(float f) { const uint32_t b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
+
+__global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ float s_val[NT / 64]; __shared__ int s_idx[NT / 64];
+  __shared__ float s_scan[NT / 64];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int V = p.V;
+  float* x = reinterpret_cast<float*>(smem);                 // [V] the row as the processors leave it
+  int* l_seq = reinterpret_cast<int*>(x + V);                // [max_len] the row's history
+  const long pos = p.pos[0];
+  const int cur = (int)pos + 1;                              // ids so far; the column this launch writes
+  if (pos >= 0 && cur < p.max_len) {                         // (uniform; a position outside the row writes nothing)
+    // ---- 0. everything this workgroup reads, requested in batches: the row, its history, its flag
+    const float* row = p.logits + (long)r * p.ld;
+    long long* seq = p.seqs + (long)r * p.max_len;
+    const bool fin = !p.unfinished[r];
+    const float u = p.uniforms ? p.uniforms[(long)r * p.max_len + cur] : 0.f;
+    for (int c = tid; c < p.max_len; c += NT) {
+      const long long w = c < cur ? seq[c] : -1;
+      l_seq[c] = (w >= 0 && w < V) ? (int)w : -1;            // (an id outside the row touches nothing below)
+    }
+    for (int w0 = tid; w0 < V; w0 += NT * UNR) {
+      float lv[UNR];
+#pragma unroll
+      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; lv[q] = w < V ? row[w] : 0.f; }
+#pragma unroll
+      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; if (w < V) x[w] = lv[q]; }
+    }
+    __syncthreads();
+    // ---- 1. repetition penalty: every distinct id of the history once (the first occurrence's thread applies it)
+    if (p.rep_penalty != 1.f) {
+      for (int c = tid; c < cur; c += NT) {
+        const int w = l_seq[c];
+        bool first = w >= 0;
+        for (int j = 0; j < c && first; ++j) first = l_seq[j] != w;
+        if (first) { const float v = x[w]; x[w] = v < 0.f ? v * p.rep_penalty : v / p.rep_penalty; }
+      }
+      __syncthreads();
+    }
+    // ---- 2. no-repeat n-grams: every earlier window of g ids that starts like the last g - 1 ids bans its own last id
+    const int g = p.ngram;
+    if (g > 0 && cur >= g) {
+      const int tail = cur - (g - 1);                        // the last g - 1 ids: l_seq[tail .. cur - 1]
+      for (int i = tid; i + g <= cur; i += NT) {
+        bool same = true;
+        for (int j = 0; j < g - 1 && same; ++j) same = l_seq[i + j] == l_seq[tail + j];
+        const int w = l_seq[i + g - 1];
+        if (same && w >= 0) x[w] = -INFINITY;                // (several windows may ban the same id: the same store)
+      }
+      __syncthreads();
+    }
+    // ---- 3. minimum length
+    if (cur < p.min_length) {
+      if (tid == 0) x[p.eos] = -INFINITY;
+      __syncthreads();
+    }
+    // ---- 4. temperature (a division, as HF's), the row's arg-max
+    float bv = -INFINITY; int bi = NONE;
+    for (int w = tid; w < V; w += NT) {
+      float v = x[w];
+      if (p.do_sample && p.temperature != 1.f) { v = v / p.temperature; x[w] = v; }      // (own entries only: no barrier needed)
+      if (v > bv) { bv = v; bi = w; }                        // ascending index: ties keep the lowest
+    }
+    block_argmax(bv, bi, s_val, s_idx);
+    const bool empty = bi == NONE || !(bv > -INFINITY) || !(bv < INFINITY);     // no entry to choose from (all -inf / NaN), or an infinite one
+    int it = bi == NONE ? p.pad : bi;
+    uint32_t thr = 0u;                                       // the smallest kept key (0: everything stays)
+    if (p.do_sample && !empty) {
+      // ---- 5. top-k: the key of the k-th largest value = the smallest m with fewer than k entries above it
+      if (p.top_k > 0 && p.top_k < V) {
+        const float k = (float)p.top_k;
+        uint32_t lo = 0x007fffffu, hi = fkey(bv);            // key(-inf) .. key(row maximum)
+        while (lo < hi) {                                    // (uniform: every thread holds the same reduction results)
+          const uint32_t mid = lo + ((hi - lo) >> 1);
+          float a = 0.f;
+          for (int w = tid; w < V; w += NT) a += fkey(x[w]) > mid ? 1.f : 0.f;
+          if (block_sum(a, s_val) < k) hi = mid; else lo = mid + 1;
+        }
+        thr = hi;
+      }
+      // ---- 6. top-p over the softmax of what top-k left: the smallest m whose mass of entries <= m exceeds (1 - p) * total
+      if (p.top_p < 1.f) {
+        auto below = [&](uint32_t m) {                       // mass of the kept entries with key <= m
+          float a = 0.f;
+          for (int w = tid; w < V; w += NT) { const uint32_t kx = fkey(x[w]); if (kx >= thr && kx <= m) a += expf(x[w] - bv); }
+          return block_sum(a, s_val);
+        };
+        const uint32_t top = fkey(bv);
+        const float limit = (1.f - p.top_p) * below(top);
+        uint32_t lo = thr > 0x007fffffu ? thr : 0x007fffffu, hi = top;          // below(top) = total > limit: the maximum always stays
+        while (lo < hi) {
+          const uint32_t mid = lo + ((hi - lo) >> 1);
+          if (below(mid) > limit) hi = mid; else lo = mid + 1;
+        }
+        thr = hi;
+      }
+      if (thr) {
+        __syncthreads();
+        for (int w = tid; w < V; w += NT) if (fkey(x[w]) < thr) x[w] = -INFINITY;
+      }
+    }
+    __syncthreads();
+    // ---- 7. the processed row leaves; total weight of the kept entries
+    float part = 0.f;
+    float* out = p.rows_out ? p.rows_out + ((long)cur * gridDim.x + r) * V : nullptr;
+    for (int w = tid; w < V; w += NT) {
+      const float v = x[w];
+      if (out) out[w] = v;
+      if (!empty) part += expf(v - bv);                      // (exp(-inf) = 0)
+    }
+    const float total = empty ? 1.f : block_sum(part, s_val);
+    // ---- 8. the draw: inverse CDF in vocabulary order -- a thread owns a contiguous piece, a wave scans its 64 pieces, wave totals meet in LDS
+    if (p.do_sample && !empty) {
+      const int C = (V + NT - 1) / NT, c0 = min(V, tid * C), c1 = min(V, c0 + C);
+      float own = 0.f;
+      for (int j = c0; j < c1; ++j) own += expf(x[j] - bv);
+      float inc = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(inc, o, 64); if (lane >= o) inc += up; }
+      __syncthreads();
+      if (lane == 63) s_scan[wave] = inc;
+      __syncthreads();
+      float base = 0.f, all = 0.f;
+#pragma unroll
+      for (int w = 0; w < NT / 64; ++w) { if (w < wave) base += s_scan[w]; all += s_scan[w]; }
+      const float target = u * all;
+      float run = base + inc - own;
+      float cv = -INFINITY; int ci = NONE;                   // the first column whose running sum exceeds the target: arg-max of (0, lowest index)
+      int last = -1;                                         // the highest kept column (target >= the rounded total: u next to 1)
+      for (int j = c0; j < c1; ++j) {
+        const float k = expf(x[j] - bv);
+        run += k;
+        if (k > 0.f) last = j;
+        if (ci == NONE && k > 0.f && run > target) { cv = 0.f; ci = j; }
+      }
+      block_argmax(cv, ci, s_val, s_idx);
+      if (ci == NONE) {
+        float lv = last < 0 ? -INFINITY : 0.f; int li = last < 0 ? NONE : -last;      // highest index = lowest negated index among equal keys
+        block_argmax(lv, li, s_val, s_idx);
+        ci = li == NONE ? it : -li;
+      }
+      it = ci;
+    }
+    // ---- 9. finished rows emit [PAD]; a row finishes when it emits [EOS]
+    if (tid == 0) {
+      float lp = empty ? 0.f : (x[it] - bv) - logf(total);
+      if (fin) { it = p.pad; lp = 0.f; }
+      else if (it == p.eos) { p.unfinished[r] = 0; atomicAdd(p.n_done, 1); }
+      seq[cur] = it;
+      p.words[r] = it;
+      if (p.tok_logp) p.tok_logp[(long)r * p.max_len + cur] = lp;
+    }
+  }
+  if (p.pos_out) {
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence();
+      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int evk_hf_sample_step(const float* logits, int32_t ld, int32_t V, int32_t R, int32_t max_len, const int64_t* pos, int32_t eos, int32_t pad,
+                       int32_t do_sample, float repetition_penalty, int32_t no_repeat_ngram, int32_t min_length, float temperature,
+                       int32_t top_k, float top_p, int64_t* seqs, unsigned char* unfinished, int64_t* words, int32_t* n_done, float* tok_logp,
+                       float* rows_out, const float* uniforms, int64_t* pos_advance, int32_t* ticket, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(logits && pos && seqs && unfinished && words && n_done && R > 0 && V > 0 && ld >= V && max_len > 1, "hf_sample_step: bad args");
+  EVK_REQUIRE(V <= V_MAX, "hf_sample_step: V = %d exceeds %d (the row is kept in LDS)", V, V_MAX);
+  EVK_REQUIRE(max_len <= LEN_MAX, "hf_sample_step: max_len = %d exceeds %d (the history is kept in LDS)", max_len, LEN_MAX);
+  EVK_REQUIRE(eos >= 0 && eos < V && pad >= 0 && pad < V, "hf_sample_step: bad token ids");
+  EVK_REQUIRE(repetition_penalty > 0.f, "hf_sample_step: repetition_penalty must be > 0 (got %g)", (double)repetition_penalty);
+  EVK_REQUIRE(no_repeat_ngram >= 0 && no_repeat_ngram <= NGRAM_MAX, "hf_sample_step: no_repeat_ngram must be in [0, %d] (got %d)", NGRAM_MAX,
+              no_repeat_ngram);
+  EVK_REQUIRE(min_length >= 0, "hf_sample_step: min_length must be >= 0");
+  EVK_REQUIRE(!do_sample || uniforms, "hf_sample_step: do_sample needs uniforms");
+  EVK_REQUIRE(!do_sample || temperature > 0.f, "hf_sample_step: temperature must be > 0 (got %g)", (double)temperature);
+  EVK_REQUIRE(!do_sample || top_k >= 0, "hf_sample_step: top_k must be >= 0 (got %d)", top_k);
+  EVK_REQUIRE(!do_sample || (top_p > 0.f && top_p <= 1.f), "hf_sample_step: top_p must be in (0, 1] (got %g)", (double)top_p);
+  EVK_REQUIRE(!pos_advance || ticket, "hf_sample_step: advancing the position needs a (zero-initialised) ticket word");
+  const size_t lds = (size_t)V * 4 + (size_t)max_len * 4;
+  HfSampleP p{logits, ld, V, max_len, eos, pad, do_sample ? 1 : 0, no_repeat_ngram, min_length, top_k, repetition_penalty, temperature, top_p,
+              reinterpret_cast<const long long*>(pos), reinterpret_cast<long long*>(seqs), unfinished, reinterpret_cast<long long*>(words),
+              n_done, tok_logp, rows_out, uniforms, reinterpret_cast<long long*>(pos_advance), ticket};
+  ProfScope ps(EVK_FAM_NORM, s);
+  hipLaunchKernelGGL(hf_sample_step_kernel, dim3(R), dim3(NT), lds, s, p);
+  return evk_check_launch("hf_sample_step");
+}
+
+}  // extern "C"

@@ -121,6 +121,10 @@ class _Holder(nn.Module):
         self.encoder_decoder = _EncDec(dec)
 
 
+# Hugging Face's neutral values of the generate() controls this backend serves
+_HF_NEUTRAL = dict(do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0)
+
+
 class DistilGPT2TextDecoderModel(nn.Module):
     def __init__(self, config, tokenizer):
         super().__init__()
@@ -135,6 +139,9 @@ class DistilGPT2TextDecoderModel(nn.Module):
         self.beam_size = config['beam_size']
         self.max_seq_len = config['max_seq_len']
         self.sample_n = int(config.get('sample_n', 1))         # default of generate(num_return_sequences=...)
+        # defaults of generate()'s Hugging Face controls: the keys of the same names, where the configuration carries them
+        self.generation = {k: config[k] for k in _HF_NEUTRAL if config.get(k) is not None}
+        self.generator = config.get('generator')
         self.p_embd = 0.1
 
     @property
@@ -168,7 +175,9 @@ class DistilGPT2TextDecoderModel(nn.Module):
         return session_usable(self, S)
 
     @torch.no_grad()
-    def generate(self, enc, num_return_sequences=None, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0):
+    def generate(self, enc, num_return_sequences=None, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, *,
+                 do_sample=None, temperature=None, top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None,
+                 min_length=None, uniforms=None, generator=None, return_logprobs=False):
         """HF beam search (num_beams = beam_size in 1..8, max_length = max_seq_len, length_penalty 1, early_stopping False) -> (B * n, L) ids
         starting with [BOS], padded with [PAD], L = min(longest, max_seq_len): the n = num_return_sequences (default: config sample_n, 1)
         best hypotheses of every study next to each other; with return_scores also their scores (B * n,) f64 = HF's sequences_scores.
@@ -177,7 +186,23 @@ class DistilGPT2TextDecoderModel(nn.Module):
         loop (_generate_host), which serves beam_size <= 4 and n = 1 only and refuses the rest with NotImplementedError.
         step_hook(t, logp, scores): test instrument, called on the launching stream before the bookkeeping of position t reads `logp`
         (f32 (B * beam, V), may be edited in place); slot / as_iterator / burst: as decode.beam_search -- the iterator returns the packed
-        result of gpt2_decode._GPT2Session._run_iter."""
+        result of gpt2_decode._GPT2Session._run_iter.
+        Sampling and logits processors (Hugging Face's names, semantics and order; None: the configuration's key of that name, else HF's
+        neutral value): do_sample (False), temperature (1.0), top_k (0), top_p (1.0), repetition_penalty (1.0), no_repeat_ngram_size (0,
+        at most 8), min_length (0).  With do_sample, or with any of repetition_penalty / no_repeat_ngram_size / min_length switched on
+        (temperature, top_k and top_p act only when do_sample, as in HF), the search is gpt2_decode._GPT2SampleSession: beam_size must
+        be 1, num_return_sequences > 1 needs do_sample, there is no host-driven route (NotImplementedError where the device session does
+        not serve the geometry).  -> (B * n, L) ids [, with return_logprobs (B * n, L) f32 log-probabilities of the chosen tokens under
+        the processed distribution, column 0 = 0] [, with return_scores their per-row sum / generated length, f64].  uniforms: f32
+        (B * n, max_seq_len) on enc's device, the numbers in [0, 1) of the inverse-CDF draws (column c draws the id of column c); absent:
+        torch.rand on the device with `generator` (default: the configuration's `generator`, else the global one).
+        step_hook(t, logits, None) on this route: before the choice at step t reads the f32 logits rows (B * n, V)."""
+        o = self._generation_options(do_sample, temperature, top_k, top_p, repetition_penalty, no_repeat_ngram_size, min_length)
+        if o is not None:
+            return self._generate_processed(enc, o, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst,
+                                            uniforms, generator)
+        if return_logprobs:
+            raise NotImplementedError('return_logprobs needs do_sample or a logits processor (the beam search returns scores)')
         nb = int(self.beam_size)
         if not 1 <= nb <= 8:
             raise ValueError('beam_size must be in [1, 8] for the distilgpt2 backend, not %d' % nb)
@@ -193,6 +218,58 @@ class DistilGPT2TextDecoderModel(nn.Module):
             raise NotImplementedError('beam_size > 4, num_return_sequences > 1, scores, step hooks and stepwise iteration need the device '
                                       'route of the distilgpt2 search')
         return self._generate_host(enc)
+
+    def _generation_options(self, do_sample, temperature, top_k, top_p, repetition_penalty, no_repeat_ngram_size, min_length):
+        """the controls of generate() resolved against the configuration and checked -> dict (keys of _HF_NEUTRAL), or None when they leave
+        the beam search as it is"""
+        given = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                     no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length)
+        o = {k: (v if v is not None else self.generation.get(k, _HF_NEUTRAL[k])) for k, v in given.items()}
+        o = dict(do_sample=bool(o['do_sample']), temperature=float(o['temperature']), top_k=int(o['top_k']), top_p=float(o['top_p']),
+                 repetition_penalty=float(o['repetition_penalty']), no_repeat_ngram_size=int(o['no_repeat_ngram_size']),
+                 min_length=int(o['min_length']))
+        if not o['temperature'] > 0:
+            raise ValueError('temperature must be > 0, not %r' % o['temperature'])
+        if not 0 < o['top_p'] <= 1:
+            raise ValueError('top_p must be in (0, 1], not %r' % o['top_p'])
+        if o['top_k'] < 0:
+            raise ValueError('top_k must be >= 0, not %r' % o['top_k'])
+        if not o['repetition_penalty'] > 0:
+            raise ValueError('repetition_penalty must be > 0, not %r' % o['repetition_penalty'])
+        if not 0 <= o['no_repeat_ngram_size'] <= 8:
+            raise ValueError('no_repeat_ngram_size must be in [0, 8], not %r' % o['no_repeat_ngram_size'])
+        if o['min_length'] < 0:
+            raise ValueError('min_length must be >= 0, not %r' % o['min_length'])
+        if not o['do_sample']:
+            # (the warpers act only on a sampling search, as in HF: a temperature the configuration carries for another route changes nothing)
+            o.update(temperature=1.0, top_k=0, top_p=1.0)
+        return None if o == _HF_NEUTRAL else o
+
+    def _generate_processed(self, enc, o, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst, uniforms,
+                            generator):
+        """generate() with do_sample or a logits processor switched on: the device session of gpt2_decode.sample"""
+        if int(self.beam_size) != 1:
+            raise NotImplementedError('sampling and logits processors need beam_size 1 (beam search with processors is not built), not %d'
+                                      % int(self.beam_size))
+        n = self.sample_n if num_return_sequences is None else int(num_return_sequences)
+        if n < 1 or (n > 1 and not o['do_sample']):
+            raise ValueError('num_return_sequences must be >= 1, and 1 without do_sample, not %d' % n)
+        R, max_len = enc.shape[0] * n, int(self.max_seq_len)
+        if uniforms is not None:
+            if not o['do_sample']:
+                raise ValueError('uniforms are the numbers of the draws: they need do_sample')
+            if (not torch.is_tensor(uniforms) or tuple(uniforms.shape) != (R, max_len) or uniforms.dtype != torch.float32 or
+                    uniforms.device != enc.device):
+                raise ValueError('uniforms must be float32 %s on %s, not %s %s on %s'
+                                 % ((R, max_len), enc.device, getattr(uniforms, 'dtype', type(uniforms)),
+                                    tuple(getattr(uniforms, 'shape', ())), getattr(uniforms, 'device', None)))
+        from . import gpt2_decode
+        if not gpt2_decode.session_usable(self, enc.shape[1], need_graph=False):
+            raise NotImplementedError('sampling and logits processors need the device route of the distilgpt2 search')
+        if self.vocab > 12288:
+            raise NotImplementedError('sampling and logits processors serve vocabularies up to 12288 entries, not %d' % self.vocab)
+        return gpt2_decode.sample(self, enc, n, o, return_logprobs, return_scores, step_hook, uniforms,
+                                  generator if generator is not None else self.generator, slot, as_iterator, burst)
 
     @torch.no_grad()
     def _generate_host(self, enc):

@@ -9,7 +9,10 @@ The whole Hugging Face beam search (classic BeamSearchScorer, length_penalty 1, 
     residual -> ln_cross_attn -> q_attn -> cross-attention (one K / V row per study, kv_div = beam) -> c_proj + residual -> ln_2 -> MLP
     (gelu_new); ln_f, the tied head into a persistent f32 buffer, log_softmax.
 The session (caches, row table, cross K / V, hypothesis arrays, captured step, replay plan) lives on the decoder and is reused by every
-batch of its geometry; decode._Session._drive supplies warm-up, capture, replay and burst yields."""
+batch of its geometry; decode._Session._drive supplies warm-up, capture, replay and burst yields.
+
+_GPT2SampleSession is the same for Hugging Face's sampling / greedy decoding with logits processors (num_beams 1): the same GPT-2 step
+without the log_softmax, and evk_hf_sample_step (csrc/hf_sample.hip) on the raw logits in place of evk_hf_beam_step."""
 import ctypes as C
 import math
 from collections import deque
@@ -26,11 +29,12 @@ _POLL = [True]           # stop issuing steps once a completed copy of the done 
 POLL_EVERY = 8           # issued steps between two non-blocking copies of the done counter
 
 
-def session_usable(dec, S=None):
-    """the device route serves this decoder (and an encoder output of S positions)"""
+def session_usable(dec, S=None, need_graph=True):
+    """the device route serves this decoder (and an encoder output of S positions); need_graph: only while graph capture is enabled (the
+    beam search then has its host-driven route; the sampling route has none and issues its steps eagerly instead)"""
     d = dec.gpt2.transformer.wte.weight.shape[1]
-    return (d % dec.heads == 0 and d // dec.heads in (64, 128, 256) and 5 <= int(dec.max_seq_len) <= 256 and decode._GRAPH_ENABLED[0] and
-            (S is None or S <= 256) and tunable('EVK_GPT2_SESSION', '1') != '0')
+    return (d % dec.heads == 0 and d // dec.heads in (64, 128, 256) and 5 <= int(dec.max_seq_len) <= 256 and
+            (decode._GRAPH_ENABLED[0] or not need_graph) and (S is None or S <= 256) and tunable('EVK_GPT2_SESSION', '1') != '0')
 
 
 def _attend(q, ldq, k, v, knew, vnew, rowmap, last_pos, R, S, heads, dh, kv_div):
@@ -92,8 +96,9 @@ class _GPT2Session(decode._Session):
                                        H.ptr(self.done), H.ptr(self.n_done), None if last else H.ptr(self.pos), H.ptr(self.ticket), H.stream()),
                 'hf_beam_step')
 
-    def _step(self):
-        """the GPT-2 block stack for the tokens in `words` at position *pos -> logp_buf; no host-side shape depends on the step index"""
+    def _trunk(self):
+        """the GPT-2 block stack and the tied head for the tokens in `words` at position *pos -> logits_buf (f32); no host-side shape depends
+        on the step index.  Shared with _GPT2SampleSession, whose bookkeeping reads the raw logits"""
         t = self.dec.gpt2.transformer
         R, d, heads, dh, nb = self.R, self.d, self.heads, self.dh, self.nb
         x = ops.embedding(self.words.view(R, 1), t.wte.weight, pos=t.wpe.weight, pos0=self.pos)
@@ -110,16 +115,19 @@ class _GPT2Session(decode._Session):
         h = t.ln_f(x)
         W, V, Np = self.dec.gpt2.lm_head.weight, self.V, self.logits_buf.shape[1]
         ops.gemm(h, ops.shadow(W, pad_rows=(V != Np)), self.logits_buf, R, V, d, lda=d, ldb=d, ldc=Np)
-        ops.log_softmax(self.logits_buf, V, out=self.logp_buf)
+
+    def _step(self):
+        """_trunk, then the log-probabilities the beam bookkeeping reads -> logp_buf"""
+        self._trunk()
+        ops.log_softmax(self.logits_buf, self.V, out=self.logp_buf)
 
     def _body(self):
         """bookkeeping of position `pos` (which also advances it), then the decoder step that writes the log-probabilities of pos + 1"""
         self._book(False)
         self._step()
 
-    def _refill(self, enc):
-        """cross-attention K / V of this batch into the session's buffers, the search state back to [BOS]; a captured step whose weights
-        have changed since is retired"""
+    def _refill_cross(self, enc):
+        """cross-attention K / V of this batch into the session's buffers; a captured step whose weights have changed since is retired"""
         dec, d = self.dec, self.d
         for i, blk in enumerate(dec.gpt2.transformer.h):
             ck, cv = blk.crossattention.c_attn(enc).split(d, dim=2)
@@ -130,6 +138,11 @@ class _GPT2Session(decode._Session):
         if key != self.weights_key:
             self._retire_plan()
             self.weights_key = key
+
+    def _refill(self, enc):
+        """_refill_cross, and the search state back to [BOS]"""
+        dec = self.dec
+        self._refill_cross(enc)
         self.seqs.fill_(dec.pad_token_id)
         self.seqs[:, 0] = dec.bos_token_id
         self.words.fill_(dec.bos_token_id)
@@ -143,11 +156,15 @@ class _GPT2Session(decode._Session):
         self.done.zero_()
         self.n_done.zero_()
 
+    def _n_units(self):
+        """what the done counter counts up to: studies"""
+        return self.B
+
     def _stopper(self):
         """-> stop(i) for _drive: every POLL_EVERY issued steps the done counter is copied to pinned memory without blocking and an event
         recorded; the newest copy whose event has completed decides.  Done studies are frozen (csrc/hf_beam.hip), so steps issued after
         the last study became done cannot change the result."""
-        polls, state, B = deque(), dict(last=0, slot=0), self.B
+        polls, state, B = deque(), dict(last=0, slot=0), self._n_units()
 
         def stop(i):
             if not _POLL[0]:
@@ -180,10 +197,110 @@ class _GPT2Session(decode._Session):
         self._book(True)                                                 # the last position: every study that is not done closes its beams
         decode._reap_plans()
         decode.stats['gpt2_steps_issued'] = self.issued + 1
+        decode.stats['gpt2_route'] = 'beam'
         packed = torch.cat([self.hyp_seq[:, :n].reshape(B * n, max_len), self.hyp_len[:, :n].reshape(B * n, 1).long()], dim=1)
         if return_scores:
             return packed, self.hyp_score[:, :n].reshape(-1).clone()
         return packed
+
+
+class _GPT2SampleSession(_GPT2Session):
+    """The session of Hugging Face's sampling / greedy decoding with logits processors over B studies x n rows: the GPT-2 step of the beam
+    session (the n copies of a study next to each other share the study's cross-attention K / V, kv_div = n; rows never trade places, so the
+    cache row table stays the identity) plus the arrays of evk_hf_sample_step (csrc/hf_sample.hip), which reads the raw logits: no
+    log_softmax launch.  The options are kernel arguments of the captured step, so they are part of the session's key (see sample())."""
+
+    def __init__(self, dec, B, n, max_len, S, dev, opts, with_logp=False, slot=0, keep_rows=False):
+        self._init_driving(dec, slot)
+        t = dec.gpt2.transformer
+        d, nl, V = t.wte.weight.shape[1], len(t.h), dec.vocab
+        R = B * n
+        self.B, self.nb, self.R, self.max_len, self.S, self.n_return = B, n, R, max_len, S, n          # (nb: rows per study, read by _trunk)
+        self.d, self.heads, self.dh, self.V = d, dec.heads, d // dec.heads, V
+        self.opts = dict(opts)
+        self.kc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
+        self.vc = [torch.empty(B, S, d, dtype=BF16, device=dev) for _ in range(nl)]
+        self.ks = [torch.zeros(R, max_len, d, dtype=BF16, device=dev) for _ in range(nl)]
+        self.vs = [torch.zeros(R, max_len, d, dtype=BF16, device=dev) for _ in range(nl)]
+        self.anc = torch.arange(R, dtype=torch.int32, device=dev).view(R, 1).expand(R, max_len).contiguous()
+        self.words = torch.empty(R, dtype=torch.long, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.long, device=dev)
+        self.logits_buf = torch.zeros(R, (V + 7) // 8 * 8, dtype=F32, device=dev)      # (pad columns zeroed once, never read by the bookkeeping)
+        self.logp_buf = self.logits_buf[:, :V]                                         # what _drive hands to a step hook: the raw logits
+        self.seqs = torch.empty(R, max_len, dtype=torch.long, device=dev)
+        self.unfinished = torch.empty(R, dtype=torch.uint8, device=dev)
+        self.n_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.uniforms = torch.empty(R, max_len, dtype=F32, device=dev) if opts['do_sample'] else None
+        self.tok_logp = torch.empty(R, max_len, dtype=F32, device=dev) if with_logp else None
+        self.rows_out = torch.empty(max_len, R, V, dtype=F32, device=dev) if keep_rows else None
+        self.pin = torch.empty(max_len // POLL_EVERY + 4, dtype=torch.int32).pin_memory()
+        self.weights_key = None
+
+    def _n_units(self):
+        """the done counter counts rows"""
+        return self.R
+
+    def _book(self, last):
+        """one launch (csrc/hf_sample.hip): processors, choice, finished rows, next tokens, and -- between steps -- the position counter's
+        increment"""
+        dec, o = self.dec, self.opts
+        H.check(H.lib.evk_hf_sample_step(H.ptr(self.logits_buf), self.logits_buf.stride(0), self.V, self.R, self.max_len, H.ptr(self.pos),
+                                         dec.eos_token_id, dec.pad_token_id, int(bool(o['do_sample'])), C.c_float(o['repetition_penalty']),
+                                         int(o['no_repeat_ngram_size']), int(o['min_length']), C.c_float(o['temperature']), int(o['top_k']),
+                                         C.c_float(o['top_p']), H.ptr(self.seqs), H.ptr(self.unfinished), H.ptr(self.words), H.ptr(self.n_done),
+                                         H.ptr(self.tok_logp) if self.tok_logp is not None else None,
+                                         H.ptr(self.rows_out) if self.rows_out is not None else None,
+                                         H.ptr(self.uniforms) if self.uniforms is not None else None,
+                                         None if last else H.ptr(self.pos), H.ptr(self.ticket), H.stream()), 'hf_sample_step')
+
+    def _body(self):
+        """the choice of column pos + 1 (which also advances pos), then the decoder step that writes the logits of the column after it"""
+        self._book(False)
+        self._trunk()
+
+    def _refill(self, enc, uniforms=None, generator=None):
+        """_refill_cross, every row back to [BOS], fresh uniform numbers (the captured step reads them from the session's buffer)"""
+        dec = self.dec
+        self._refill_cross(enc)
+        self.seqs.fill_(dec.pad_token_id)
+        self.seqs[:, 0] = dec.bos_token_id
+        self.words.fill_(dec.bos_token_id)
+        self.unfinished.fill_(1)
+        self.pos.zero_()
+        self.ticket.zero_()
+        self.n_done.zero_()
+        if self.tok_logp is not None:
+            self.tok_logp.zero_()
+        if self.uniforms is not None:
+            if uniforms is not None:
+                self.uniforms.copy_(uniforms)
+            else:
+                torch.rand(self.uniforms.shape, generator=generator, dtype=F32, device=self.uniforms.device, out=self.uniforms)
+
+    def _run_iter(self, enc, return_logprobs=False, return_scores=False, step_hook=None, burst=0, uniforms=None, generator=None):
+        """-> packed (B * n, max_len + 1) int64: ids padded with [PAD], the last column the row's length in columns ([BOS] and [EOS]
+        included; unpack() trims) [, tok_logp (B * n, max_len) f32] [, scores (B * n,) f64 = sum of the chosen tokens' log-probabilities /
+        generated length].  Yields as _GPT2Session._run_iter does."""
+        max_len, eos = self.max_len, self.dec.eos_token_id
+        hook = step_hook if step_hook is not None else (lambda *a: None)
+        self._refill(enc, uniforms, generator)
+        self._trunk()                                                    # position 0: every row reads [BOS]
+        hook(0, self.logp_buf, None)
+        # body number i chooses column i + 1 from the logits of position i and writes those of position i + 1
+        yield from self._drive(max_len - 2, 1, step_hook, burst, (None,), stop=self._stopper())
+        self._book(True)                                                 # the last column: nothing follows it
+        decode._reap_plans()
+        decode.stats['gpt2_steps_issued'] = self.issued + 1
+        decode.stats['gpt2_route'] = 'sample'
+        ended = self.seqs[:, 1:] == eos
+        lens = torch.where(ended.any(1), ended.int().argmax(1) + 2, torch.full_like(self.seqs[:, 0], max_len))
+        out = [torch.cat([self.seqs, lens.view(-1, 1)], dim=1)]
+        if return_logprobs:
+            out.append(self.tok_logp.clone())
+        if return_scores:
+            out.append(self.tok_logp.double().sum(1) / (lens - 1).double())
+        return out[0] if len(out) == 1 else tuple(out)
 
 
 def unpack(packed, host=None):
@@ -208,3 +325,22 @@ def search(dec, enc, n_return, return_scores=False, step_hook=None, slot=0, as_i
     if return_scores:
         return unpack(out[0]).contiguous(), out[1]
     return unpack(out).contiguous()
+
+
+def sample(dec, enc, n, opts, return_logprobs=False, return_scores=False, step_hook=None, uniforms=None, generator=None, slot=0,
+           as_iterator=False, burst=0):
+    """the sampling / processor route of DistilGPT2TextDecoderModel.generate (opts: the controls resolved and validated by generate);
+    as_iterator: a generator that yields after every issued step and returns the PACKED result (see _GPT2SampleSession._run_iter)"""
+    B, S, dev = enc.shape[0], enc.shape[1], enc.device
+    max_len = int(dec.max_seq_len)
+    with_logp = bool(return_logprobs or return_scores)
+    key = ('gpt2-sample', B, n, max_len, S, dev.index, slot, tuple(sorted(opts.items())), with_logp)
+    ses = decode._session_for(dec, key, lambda: _GPT2SampleSession(dec, B, n, max_len, S, dev, opts, with_logp, slot))
+    enc = enc.contiguous()
+    if as_iterator:
+        return ses.run_iter(enc, return_logprobs, return_scores, step_hook, burst, uniforms, generator)
+    out = ses.run(enc, return_logprobs, return_scores, step_hook, 0, uniforms, generator)
+    if not isinstance(out, tuple):
+        return unpack(out).contiguous()
+    L = unpack(out[0]).shape[1]
+    return (out[0][:, :L].contiguous(),) + tuple(o[:, :L].contiguous() if o.dim() == 2 else o for o in out[1:])

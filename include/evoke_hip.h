@@ -545,6 +545,28 @@ int evk_sample_step(const float* logp, int32_t ld, int32_t V1, int32_t R, int32_
                     int32_t block_rows, int32_t decoding_constraint, float temperature, int32_t method, float param, int64_t* seq,
                     unsigned char* unfinished, int64_t* words, float* seq_logprobs, const float* uniforms, int64_t* pos_advance,
                     int32_t* ticket, evk_stream_t stream);
+/* One launch for everything Hugging Face's `generate` does between two decoder steps at num_beams 1 (hf_sample.hip): the standard logits
+ * processors, the choice and the finished-row bookkeeping, for R independent rows.  logits [R][ld] f32 RAW logits (V valid columns,
+ * V <= 12288; columns V .. ld-1 are never read); *pos = last filled column of seqs, cur_len = *pos + 1 ids so far including [BOS]
+ * (max_len <= 256), the history of a row is seqs[r][0 .. cur_len-1].  In HF's order, all in f32:
+ *   repetition_penalty rp > 0 (1 = off): every distinct id w of the history once, x[w] = x[w] < 0 ? x[w] * rp : x[w] / rp;
+ *   no_repeat_ngram g in [0, 8] (0 = off): if cur_len >= g, every earlier window of g ids whose first g-1 ids equal the last g-1 ids of the
+ *   history bans its own last id, x[w] = -inf (g = 1 bans every id present);  min_length: cur_len < min_length -> x[eos] = -inf;
+ *   with do_sample != 0 only: x = x / temperature (a division; temperature > 0);  top_k (0 = off): with k = min(top_k, V) every entry strictly
+ *   below the k-th largest value becomes -inf (ties with it stay);  top_p in (0, 1] (1 = off): with the softmax of the row as it stands, w stays
+ *   iff the probability mass of all entries <= x[w] exceeds 1 - p (the maximum always stays, equal values stay or leave together).
+ * Choice: do_sample -> inverse CDF over the kept entries in column order with u = uniforms[r][cur_len] (f32 [R][max_len] in [0, 1), required):
+ * the first kept column whose running weight exceeds u * total, the highest kept column if rounding leaves none; else the arg-max, ties to
+ * the lowest id.  A row without a finite entry chooses `pad`.  Bookkeeping: unfinished uint8 [R] (in / out, set to 1 by the caller before
+ * the first step): a finished row emits `pad`, a row that emits `eos` finishes and counts once in *n_done (int32, +=); the id goes to
+ * seqs[r][cur_len] (int64 [R][max_len]) and words [R] (the next decoder input).  tok_logp f32 [R][max_len] or NULL: column cur_len receives
+ * the chosen token's log-probability under the processed row, x[w] - logsumexp(x), 0 for a finished row (and for a row without a finite
+ * entry).  rows_out f32 [max_len][R][V] or NULL: slice cur_len receives the processed rows (finished rows included).
+ * pos_advance / ticket as in evk_beam_step: the last workgroup to finish writes *pos_advance = *pos + 1 and leaves the ticket at zero. */
+int evk_hf_sample_step(const float* logits, int32_t ld, int32_t V, int32_t R, int32_t max_len, const int64_t* pos, int32_t eos, int32_t pad,
+                       int32_t do_sample, float repetition_penalty, int32_t no_repeat_ngram, int32_t min_length, float temperature,
+                       int32_t top_k, float top_p, int64_t* seqs, unsigned char* unfinished, int64_t* words, int32_t* n_done, float* tok_logp,
+                       float* rows_out, const float* uniforms, int64_t* pos_advance, int32_t* ticket, evk_stream_t stream);
 /* F.normalize(p=2, eps=1e-12) rows, f32 */
 int evk_l2norm_fwd(const float* x, float* y, float* nrm, int64_t rows, int32_t D, evk_stream_t stream);
 int evk_l2norm_bwd(const float* dy, const float* y, const float* nrm, float* dx, int64_t rows, int32_t D, evk_stream_t stream);

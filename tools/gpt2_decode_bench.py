@@ -4,7 +4,11 @@ DistilGPT2TextDecoderModel.generate(); per run: wall seconds, tokens/s (studies 
 where the search runs as a device session -- the per-token step time from the HIP events of the token loop and the launches of one
 captured step.  Uses only the public generate(), so the same file measures a commit from before the device session.
 
-    python tools/gpt2_decode_bench.py [--studies 32] [--beam 3] [--max-seq-len 100] [--runs 3]"""
+--do-sample / --top-k / --top-p / --repetition-penalty time the sampling route (gpt2_decode._GPT2SampleSession, --beam 1) instead; the
+uniform numbers are drawn once, outside the timed calls, so that every run draws the same reports.
+
+    python tools/gpt2_decode_bench.py [--studies 32] [--beam 3] [--max-seq-len 100] [--runs 3]
+                                      [--do-sample] [--top-k K] [--top-p P] [--repetition-penalty RP]"""
 import argparse
 import json
 import os
@@ -23,6 +27,10 @@ def main():
     ap.add_argument('--beam', type=int, default=3)
     ap.add_argument('--max-seq-len', type=int, default=100)
     ap.add_argument('--runs', type=int, default=3)
+    ap.add_argument('--do-sample', action='store_true')
+    ap.add_argument('--top-k', type=int, default=0)
+    ap.add_argument('--top-p', type=float, default=1.0)
+    ap.add_argument('--repetition-penalty', type=float, default=1.0)
     a = ap.parse_args()
     from evoke_amd import decode, ops
     from evoke_amd.config import ARGS
@@ -40,12 +48,17 @@ def main():
     dec = dec.cuda().eval()
     ops.set_dropout_enabled(False)
     enc = (S.det((a.studies, 50, d), a=.013, b=.007, c=.3) * 0.5).to(ops.BF16).cuda()
+    kw = {}
+    if a.do_sample or a.repetition_penalty != 1.0:                       # (no keyword at all otherwise: the call a commit without them accepts)
+        kw = dict(do_sample=a.do_sample, top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty)
+        if a.do_sample:
+            kw['uniforms'] = torch.rand(a.studies, a.max_seq_len, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1))
     runs = []
     for i in range(2 + a.runs):
         decode.stats.pop('step_events', None)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        seq = dec.generate(enc)
+        seq = dec.generate(enc, **kw)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = dict(seconds=round(dt, 4), width=int(seq.shape[1]), tokens_per_s=round(a.studies * (seq.shape[1] - 1) / dt, 1))
@@ -56,7 +69,8 @@ def main():
             rec['steps_issued'] = decode.stats.get('gpt2_steps_issued')
         if i >= 2:
             runs.append(rec)
-    print(json.dumps(dict(studies=a.studies, beam=a.beam, max_seq_len=a.max_seq_len, device_session=bool(getattr(dec, 'session_available', lambda *_: False)(50)),
+    print(json.dumps(dict(studies=a.studies, beam=a.beam, max_seq_len=a.max_seq_len, route=decode.stats.get('gpt2_route', 'beam'),
+                          options={k: v for k, v in kw.items() if k != 'uniforms'}, device_session=bool(getattr(dec, 'session_available', lambda *_: False)(50)),
                           runs=runs)))
 
 
