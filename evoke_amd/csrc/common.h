@@ -54,13 +54,33 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// exp(d) that keeps the f32 subnormals: the fast exponential flushes results below 2^-126 (d < -87.3) to 0, where the bf16 storage format still
+// has patterns (down to 1e-40).  The argument is moved into the normal range and the factor exp(-64) applied afterwards.  Used by the softmax
+// of norm.hip and by logistic() below; from -80 up it is __expf itself.
+__device__ __forceinline__ float exp_tail(float d) { return d < -80.f ? __expf(d + 64.f) * 1.603810890548638e-28f : __expf(d); }
+
+// 1 / (1 + exp(-t)).  Below -80 the sum is 1 in f32 (and exp(-t) overflows from 88.7 on): the result is exp(t)
+__device__ __forceinline__ float logistic(float t) { return t < -80.f ? exp_tail(t) : 1.f / (1.f + __expf(-t)); }
+
 __device__ __forceinline__ float act_apply(float x, int act) {
   switch (act) {
     case EVK_ACT_RELU: return fmaxf(x, 0.f);
-    case EVK_ACT_GELU: return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
+    // 1 + erf(x / sqrt 2) cancels in the lower tail (at x = -5 the f32 sum keeps 3 bits): erfc does not.  Above -3 the sum is >= 2.7e-3 and
+    // good to 2e-5 relative, a twentieth of a 16-bit ulp
+    case EVK_ACT_GELU: return x < -3.f ? 0.5f * x * erfcf(x * -0.70710678118654752f) : 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
     case EVK_ACT_TANH: return tanhf(x);
-    case EVK_ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
-    case EVK_ACT_GELU_NEW: return 0.5f * x * (1.f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
+    case EVK_ACT_SIGMOID: return logistic(x);
+    case EVK_ACT_GELU_NEW: {        // 0.5 (1 + tanh u) == 1 / (1 + exp(-2 u)): the left side cancels for u << 0, the right side does not
+      const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+      // the switch sits where the cancelling form stops being good to half a unit of the storage format: 1 + tanh(u) carries 2^-25 absolute,
+      // fp16 (11 bits, subnormal below 6e-5) needs the tail form from u = -3 on, bf16 (8 bits) from u = -5.5 on
+#ifdef EVK_STORE_BF16
+      constexpr float kTail = -5.5f;
+#else
+      constexpr float kTail = -3.f;
+#endif
+      return u < kTail ? x * logistic(2.f * u) : 0.5f * x * (1.f + tanhf(u));
+    }
     default: return x;
   }
 }

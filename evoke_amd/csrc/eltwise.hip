@@ -42,7 +42,8 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__
 __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ ref,
                                                       bf16_t* __restrict__ dx, long n, int act) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float g = bf2f(dy[i]), r = bf2f(ref[i]);
+    const float g = bf2f(dy[i]);
+    float r = bf2f(ref[i]);
     float d;
     switch (act) {
       case EVK_ACT_RELU: d = r > 0.f ? 1.f : 0.f; break;
@@ -50,6 +51,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16_t* __restrict__
       case EVK_ACT_SIGMOID: d = r * (1.f - r); break;
       case EVK_ACT_GELU: d = 0.5f * (1.f + erff(r * 0.70710678118654752f)) + r * 0.3989422804014327f * __expf(-0.5f * r * r); break;
       case EVK_ACT_GELU_NEW: {
+        r = fminf(fmaxf(r, -1e9f), 1e9f);      // r * r overflows f32 beyond 1.8e19 (bf16 storage reaches 3.4e38): 0 * inf below; the derivative is 0 / 1 long before
         const float u = 0.7978845608028654f * (r + 0.044715f * r * r * r), th = tanhf(u);
         d = 0.5f * (1.f + th) + 0.5f * r * (1.f - th * th) * 0.7978845608028654f * (1.f + 3.f * 0.044715f * r * r);
       } break;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const SmP p) {
   mx = wave_max(mx);
   float sum = 0.f;
 #pragma unroll
-  for (int c = 0; c < SMC; ++c) { v[c] = (v[c] == -INFINITY) ? 0.f : __expf(v[c] - mx); sum += v[c]; }
+  for (int c = 0; c < SMC; ++c) { v[c] = (v[c] == -INFINITY) ? 0.f : exp_tail(v[c] - mx); sum += v[c]; }
   sum = wave_sum(sum);
   const float inv = sum > 0.f ? 1.f / sum : 0.f;
   const float sc = p.p_drop > 0.f ? 1.f / (1.f - p.p_drop) : 1.f;

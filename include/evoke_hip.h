@@ -449,6 +449,8 @@ int evk_log_softmax_scaled(const float* logits, float* logp, int64_t rows, int32
  * sums: the caller adds the rows up (a tree reduction: the same bits on every run), lse as above.  loss.py:9-22 */
 int evk_log_softmax_nll_rows(const float* logits, float* lse, const int64_t* target, const float* wmask, float* row_nll, int64_t rows,
                              int32_t V, int32_t ld, evk_stream_t stream);
+/* dlogits = (softmax - onehot) * wmask[row] * gscale[0] in the 16-bit storage format, pad columns [V, ld_out) = 0.  softmax = exp(logit - lse)
+ * by the fast exponential: a probability below the smallest normal f32 (2^-126) is flushed to 0. */
 int evk_nll_bwd(const float* logits, const float* lse, const int64_t* target, const float* wmask, const float* gscale,
                 void* dlogits, int64_t rows, int32_t V, int32_t ld, int32_t ld_out, evk_stream_t stream);
 /* beam step (caption_model.py:70-74): k <= 8 largest of each row, descending, ties -> lowest index first */
