@@ -11,12 +11,17 @@
 //      column *pos + 1, the row table's next column is seeded, and the last workgroup to finish advances the position.
 // A study that is done emits [PAD] from its first row for ever and never touches its list again, so steps issued after every study is
 // done change nothing that is returned.
+// evk_hf_beam_step_opts is the same kernel body (a template parameter switches the additions on) with what `generate` adds to a beam search
+// when it is asked for them: RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinLengthLogitsProcessor on the
+// log-probability rows of the running beams, each from its own history, before the candidates are formed (a pre-pass that edits `logp` in
+// place), and the scorer's length_penalty (a host-computed table of divisors cur_len ** length_penalty) and early_stopping.
 #include <stdlib.h>
 #include "common.h"
 
 namespace {
 
 constexpr int NBMAX = 8;
+constexpr int NGRAM_MAX = 8;
 
 struct HfBeamP {
   const float* logp; int ld;           // [B*nb][ld] f32 log-probs of the step, V valid columns
@@ -30,10 +35,17 @@ struct HfBeamP {
   long long* hyp_seq;                  // [B][nb][max_len] with the leading [BOS], padded with `pad`
   unsigned char* done; int* n_done;    // [B] flags (in / out); *n_done += studies that became done in this launch
   long long* pos_out; int* ticket;     // the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
+  static constexpr bool kOpts = false;
+};
+struct HfBeamOptsP : HfBeamP {         // what evk_hf_beam_step_opts adds
+  const double* len_div;               // [max_len + 1] divisor of a hypothesis that ends at cur_len, or null (= cur_len)
+  float rep_penalty;                   // (logp is written: the processors edit the rows of a study that is not done in place)
+  int ctl;                             // no_repeat_ngram_size | early_stopping << 4 | min(min_length, max_len) << 8 (one word: scalar registers are short)
+  static constexpr bool kOpts = true;
 };
 
-template <int K2>                      // capacity of a thread's candidate list: >= 2 * nb
-__global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
+template <int K2, class P>             // K2: capacity of a thread's candidate list, >= 2 * nb; P: HfBeamP or HfBeamOptsP
+__global__ __launch_bounds__(256) void hf_beam_step_kernel(const P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float s_val[4]; __shared__ int s_idx[4];
   __shared__ float win_v[2 * NBMAX]; __shared__ int win_i[2 * NBMAX];
@@ -50,6 +62,43 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
   int* l_anc = reinterpret_cast<int*>(l_seq + (size_t)nb * p.max_len);                 // [nb][anc_cols]
   for (int i = tid; i < nb * p.max_len; i += 256) l_seq[i] = seq[i];
   if (p.anc) for (int i = tid; i < nb * p.anc_cols; i += 256) l_anc[i] = p.anc[(long)b * nb * p.anc_cols + i];
+  if constexpr (P::kOpts) {
+    // ---- 0b. the logits processors in HF's order on the rows of the nb running beams, each from its own history l_seq[j][0 .. cur - 1]
+    if (!was_done) {                                           // (block-uniform, like every condition around a barrier below)
+      __syncthreads();                                         // the histories are in LDS
+      const int ml = p.max_len, cur = min((int)pos + 1, ml);      // ids so far, [BOS] included
+      float* rows = const_cast<float*>(p.logp) + (long)b * nb * p.ld;
+      if (p.rep_penalty != 1.f) {
+        // every distinct id of a history once: the thread that holds its first occurrence rewrites the entry
+        for (int j = 0; j < nb; ++j) {
+          const long long* h = l_seq + j * ml;
+          for (int c = tid; c < cur; c += 256) {
+            const long long w = h[c];
+            bool first = w >= 0 && w < V;
+            for (int q = 0; q < c && first; ++q) first = h[q] != w;
+            if (first) { float* x = rows + (long)j * p.ld + w; const float v = *x; *x = v < 0.f ? v * p.rep_penalty : v / p.rep_penalty; }
+          }
+        }
+        __syncthreads();                                       // a ban below must not be overwritten by a penalty's read-modify-write
+      }
+      const int g = p.ctl & 15;
+      if (g > 0 && cur >= g) {
+        // every earlier window of g ids that starts like the last g - 1 ids bans its own last id (several windows: the same store)
+        const int nwin = cur - g + 1, tail = cur - (g - 1);
+        for (int j = 0; j < nb; ++j) {
+          const long long* h = l_seq + j * ml;
+          for (int c = tid; c < nwin; c += 256) {
+            bool same = true;
+            for (int q = 0; q < g - 1 && same; ++q) same = h[c + q] == h[tail + q];
+            const long long w = h[c + g - 1];
+            if (same && w >= 0 && w < V) rows[(long)j * p.ld + w] = -INFINITY;
+          }
+        }
+      }
+      if (cur < (p.ctl >> 8) && tid < nb) rows[(long)tid * p.ld + p.eos] = -INFINITY;
+      __syncthreads();                                         // the rows are re-read by this workgroup only
+    }
+  }
   if (!was_done) {
     // ---- 1. the 2 * nb best candidates, descending
     float bv[K2]; int bi[K2];
@@ -107,7 +156,8 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
     if (was_done) {
       for (int k = 0; k < nb; ++k) { nx_sc[k] = 0.f; nx_tok[k] = p.pad; nx_src[k] = 0; }
     } else {
-      const double cur_len = (double)(pos + 1);
+      double cur_len = (double)(pos + 1);                      // what a sum is divided by: cur_len ** length_penalty
+      if constexpr (P::kOpts) { if (p.len_div) cur_len = p.len_div[pos + 1]; }
       int nx_rank[NBMAX];
       for (int k = 0; k < nb; ++k) { f_sc[k] = p.hyp_score[b * nb + k]; f_ln[k] = p.hyp_len[b * nb + k]; f_src[k] = k; }
       // an entry enters below every entry that is at least as good (Python's stable sort of the appended list), the list is cut to nb;
@@ -131,7 +181,8 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
         ++k;
       }
       for (; k < nb; ++k) { nx_sc[k] = -INFINITY; nx_tok[k] = p.pad; nx_src[k] = 0; nx_rank[k] = 0; }     // (V >= 2 * nb: never taken on finite rows)
-      const bool now_done = f_ln[nb - 1] != 0 && f_sc[nb - 1] >= (double)win_v[0] / cur_len;
+      bool now_done = f_ln[nb - 1] != 0 && f_sc[nb - 1] >= (double)win_v[0] / cur_len;
+      if constexpr (P::kOpts) { if (p.ctl & 16) now_done = f_ln[nb - 1] != 0; }
       if (now_done) { p.done[b] = 1; atomicAdd(p.n_done, 1); }
       else if (p.force_end)
         for (int j = 0; j < nb; ++j) insert((double)nx_sc[j] / cur_len, nx_rank[j]);
@@ -178,13 +229,10 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const HfBeamP p) {
 
 }  // namespace
 
-extern "C" {
-
-int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
-                     int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
-                     double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
-                     int32_t* ticket, evk_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// argument checks shared by the two entry points -> staging bytes, or -1 (evk_last_error says why)
+static long hf_beam_check(const float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, float* scores,
+                          int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols, double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq,
+                          unsigned char* done, int32_t* n_done, int64_t* pos_advance, int32_t* ticket) {
   EVK_REQUIRE(nb >= 1 && nb <= NBMAX, "hf_beam_step: nb must be in [1, %d] (got %d)", NBMAX, nb);
   EVK_REQUIRE(V >= 2 * nb && (int64_t)nb * V < INT32_MAX, "hf_beam_step: V=%d must hold 2 * nb = %d candidates", V, 2 * nb);
   EVK_REQUIRE(ld >= V, "hf_beam_step: ld=%d < V=%d", ld, V);
@@ -194,14 +242,55 @@ int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32
   EVK_REQUIRE(!pos_advance || ticket, "hf_beam_step: advancing the position needs a (zero-initialised) ticket word");
   const size_t lds = (size_t)nb * max_len * 8 + (anc ? (size_t)nb * anc_cols * 4 : 0);
   EVK_REQUIRE(lds <= 48000, "hf_beam_step: %zu bytes of per-study state do not fit the staging buffer", lds);
+  return (long)lds;
+}
+
+template <class P>
+static void hf_beam_launch(const P& p, int nb, int B, size_t lds, hipStream_t s) {
+  if (nb <= 2) hipLaunchKernelGGL((hf_beam_step_kernel<4, P>), dim3(B), dim3(256), lds, s, p);
+  else if (nb <= 4) hipLaunchKernelGGL((hf_beam_step_kernel<8, P>), dim3(B), dim3(256), lds, s, p);
+  else hipLaunchKernelGGL((hf_beam_step_kernel<16, P>), dim3(B), dim3(256), lds, s, p);
+}
+
+extern "C" {
+
+int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                     int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
+                     double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
+                     int32_t* ticket, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const long lds = hf_beam_check(logp, ld, V, nb, B, max_len, pos, scores, seqs, words, anc, anc_cols, hyp_score, hyp_len, hyp_seq, done, n_done,
+                                 pos_advance, ticket);
+  if (lds < 0) return -1;
   HfBeamP p{logp, ld, V, nb, max_len, eos, pad, force_end, reinterpret_cast<const long long*>(pos), scores, reinterpret_cast<long long*>(seqs),
             reinterpret_cast<long long*>(words), anc, anc_cols, hyp_score, hyp_len, reinterpret_cast<long long*>(hyp_seq), done, n_done,
             reinterpret_cast<long long*>(pos_advance), ticket};
   ProfScope ps(EVK_FAM_NORM, s);
-  if (nb <= 2) hipLaunchKernelGGL(hf_beam_step_kernel<4>, dim3(B), dim3(256), lds, s, p);
-  else if (nb <= 4) hipLaunchKernelGGL(hf_beam_step_kernel<8>, dim3(B), dim3(256), lds, s, p);
-  else hipLaunchKernelGGL(hf_beam_step_kernel<16>, dim3(B), dim3(256), lds, s, p);
+  hf_beam_launch(p, nb, B, (size_t)lds, s);
   return evk_check_launch("hf_beam_step");
+}
+
+int evk_hf_beam_step_opts(float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                          int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
+                          double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
+                          int32_t* ticket, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const double* len_div,
+                          int32_t early_stopping, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(repetition_penalty > 0.f, "hf_beam_step_opts: repetition_penalty must be > 0 (got %g)", (double)repetition_penalty);
+  EVK_REQUIRE(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= NGRAM_MAX, "hf_beam_step_opts: no_repeat_ngram_size must be in [0, %d] (got %d)",
+              NGRAM_MAX, no_repeat_ngram_size);
+  EVK_REQUIRE(min_length >= 0, "hf_beam_step_opts: min_length must be >= 0 (got %d)", min_length);
+  const long lds = hf_beam_check(logp, ld, V, nb, B, max_len, pos, scores, seqs, words, anc, anc_cols, hyp_score, hyp_len, hyp_seq, done, n_done,
+                                 pos_advance, ticket);
+  if (lds < 0) return -1;
+  EVK_REQUIRE(eos >= 0 && eos < V, "hf_beam_step_opts: eos=%d outside the %d valid columns", eos, V);
+  HfBeamOptsP p{{logp, ld, V, nb, max_len, eos, pad, force_end, reinterpret_cast<const long long*>(pos), scores, reinterpret_cast<long long*>(seqs),
+                 reinterpret_cast<long long*>(words), anc, anc_cols, hyp_score, hyp_len, reinterpret_cast<long long*>(hyp_seq), done, n_done,
+                 reinterpret_cast<long long*>(pos_advance), ticket},
+                len_div, repetition_penalty, no_repeat_ngram_size | (early_stopping ? 16 : 0) | (min_length < max_len ? min_length : max_len) << 8};
+  ProfScope ps(EVK_FAM_NORM, s);
+  hf_beam_launch(p, nb, B, (size_t)lds, s);
+  return evk_check_launch("hf_beam_step_opts");
 }
 
 }  // extern "C"

@@ -5,7 +5,10 @@ The reference class wraps HF GPT2LMHeadModel(add_cross_attention=True) in an Enc
 state_dict keys are `decoder.encoder_decoder.decoder.{transformer.{wte,wpe,h.<i>.*,ln_f},lm_head}.*` (HF Conv1D weights are
 (in, out)).  Same constructor `(config, tokenizer)`, same `forward(encoder_hidden_states, encoder_attention_mask,
 input_ids, attention_mask, stage)`; `stage='train'` returns the un-shifted cross-entropy of lines 252-254, `stage='test'`
-HF-style beam search (2*num_beams candidates, length-normalised finished hypotheses) with K/V caches.
+HF-style beam search (2*num_beams candidates, length-normalised finished hypotheses) with K/V caches; generate() also serves HF's
+sampling / greedy decoding with logits processors (num_beams 1) and beam search with the repetition_penalty / no_repeat_ngram_size /
+min_length processors, length_penalty, early_stopping and an explicit num_beams (configuration keys num_beams, early_stopping,
+gpt2_length_penalty).
 Selected in FineTune by args['text_decoder'] = 'distilgpt2' (the key exists only as a comment in modules/utils.py:78)."""
 import math
 
@@ -123,6 +126,8 @@ class _Holder(nn.Module):
 
 # Hugging Face's neutral values of the generate() controls this backend serves
 _HF_NEUTRAL = dict(do_sample=False, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0)
+# the beam controls of generate(): keyword -> configuration key (`length_penalty` itself is the R2Gen decoder's string form in the args)
+_BEAM_KEYS = dict(num_beams='num_beams', length_penalty='gpt2_length_penalty', early_stopping='early_stopping')
 
 
 class DistilGPT2TextDecoderModel(nn.Module):
@@ -141,6 +146,7 @@ class DistilGPT2TextDecoderModel(nn.Module):
         self.sample_n = int(config.get('sample_n', 1))         # default of generate(num_return_sequences=...)
         # defaults of generate()'s Hugging Face controls: the keys of the same names, where the configuration carries them
         self.generation = {k: config[k] for k in _HF_NEUTRAL if config.get(k) is not None}
+        self.beam_controls = {k: config[c] for k, c in _BEAM_KEYS.items() if config.get(c) is not None}
         self.generator = config.get('generator')
         self.p_embd = 0.1
 
@@ -177,7 +183,8 @@ class DistilGPT2TextDecoderModel(nn.Module):
     @torch.no_grad()
     def generate(self, enc, num_return_sequences=None, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, *,
                  do_sample=None, temperature=None, top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None,
-                 min_length=None, uniforms=None, generator=None, return_logprobs=False):
+                 min_length=None, uniforms=None, generator=None, return_logprobs=False, num_beams=None, length_penalty=None,
+                 early_stopping=None):
         """HF beam search (num_beams = beam_size in 1..8, max_length = max_seq_len, length_penalty 1, early_stopping False) -> (B * n, L) ids
         starting with [BOS], padded with [PAD], L = min(longest, max_seq_len): the n = num_return_sequences (default: config sample_n, 1)
         best hypotheses of every study next to each other; with return_scores also their scores (B * n,) f64 = HF's sequences_scores.
@@ -196,7 +203,22 @@ class DistilGPT2TextDecoderModel(nn.Module):
         the processed distribution, column 0 = 0] [, with return_scores their per-row sum / generated length, f64].  uniforms: f32
         (B * n, max_seq_len) on enc's device, the numbers in [0, 1) of the inverse-CDF draws (column c draws the id of column c); absent:
         torch.rand on the device with `generator` (default: the configuration's `generator`, else the global one).
-        step_hook(t, logits, None) on this route: before the choice at step t reads the f32 logits rows (B * n, V)."""
+        step_hook(t, logits, None) on this route: before the choice at step t reads the f32 logits rows (B * n, V).
+        Beam controls (None: the configuration's key, else the neutral value): num_beams (key num_beams; else beam_size), length_penalty
+        (key gpt2_length_penalty; 1.0: a hypothesis score is its sum / cur_len ** length_penalty), early_stopping (key early_stopping; False;
+        a bool -- "never" does not exist in the reference's pinned transformers).  While no num_beams is given and the other two are
+        neutral, everything above holds unchanged.  Otherwise the search is a beam search of width num_beams (else beam_size) in 1..8 with
+        num_return_sequences <= width, on which repetition_penalty, no_repeat_ngram_size and min_length act as in HF's beam mode -- on the
+        log-probability rows of every running beam, from that beam's own history -- through gpt2_decode._GPT2BeamOptionsSession (the plain
+        beam session at that width when every option is neutral).  There is no host-driven route for it (NotImplementedError where the
+        device session does not serve the geometry; with graph capture disabled the steps are issued eagerly); do_sample (beam sampling)
+        and return_logprobs are refused with NotImplementedError."""
+        bc = self._beam_controls(num_beams, length_penalty, early_stopping)
+        if bc is not None:
+            return self._generate_beam_options(enc, bc, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst,
+                                               uniforms, dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                                              repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                                              min_length=min_length))
         o = self._generation_options(do_sample, temperature, top_k, top_p, repetition_penalty, no_repeat_ngram_size, min_length)
         if o is not None:
             return self._generate_processed(enc, o, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst,
@@ -245,12 +267,58 @@ class DistilGPT2TextDecoderModel(nn.Module):
             o.update(temperature=1.0, top_k=0, top_p=1.0)
         return None if o == _HF_NEUTRAL else o
 
+    def _beam_controls(self, num_beams, length_penalty, early_stopping):
+        """the beam controls of generate() resolved against the configuration and checked -> dict(num_beams = the width, length_penalty,
+        early_stopping), or None when no num_beams is given and the scorer's controls are neutral (generate() then is what it was)"""
+        given = dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+        c = {k: (v if v is not None else self.beam_controls.get(k)) for k, v in given.items()}
+        es = False if c['early_stopping'] is None else c['early_stopping']
+        if isinstance(es, str):
+            raise ValueError('early_stopping must be a bool: %r (and "never" in particular) does not exist in the pinned transformers 4.23.1' % es)
+        if not isinstance(es, (bool, int)) or es not in (0, 1):
+            raise ValueError('early_stopping must be a bool, not %r' % (es,))
+        lp = 1.0 if c['length_penalty'] is None else c['length_penalty']
+        if isinstance(lp, (str, bool)) or not math.isfinite(float(lp)):
+            raise ValueError('length_penalty must be a finite number, not %r' % (lp,))
+        lp, es = float(lp), bool(es)
+        if c['num_beams'] is None and lp == 1.0 and not es:
+            return None
+        nb = int(self.beam_size if c['num_beams'] is None else c['num_beams'])
+        if not 1 <= nb <= 8:
+            raise ValueError('num_beams must be in [1, 8] for the distilgpt2 backend, not %d' % nb)
+        return dict(num_beams=nb, length_penalty=lp, early_stopping=es)
+
+    def _generate_beam_options(self, enc, bc, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst, uniforms,
+                               controls):
+        """generate() with a beam control given: the device beam search at width bc['num_beams'] with the processors and scorer controls"""
+        o = self._generation_options(**controls) or dict(_HF_NEUTRAL)
+        if o['do_sample']:
+            raise NotImplementedError('do_sample with num_beams / length_penalty / early_stopping is beam sampling, which is not built '
+                                      '(it differs between the pinned and later transformers releases)')
+        if return_logprobs:
+            raise NotImplementedError('return_logprobs is not built on the beam route (the beam search returns scores)')
+        if uniforms is not None:
+            raise ValueError('uniforms are the numbers of the draws: they need do_sample')
+        nb = bc['num_beams']
+        n = self.sample_n if num_return_sequences is None else int(num_return_sequences)
+        if not 1 <= n <= nb:
+            raise ValueError('num_return_sequences must be in [1, num_beams = %d], not %d' % (nb, n))
+        if self.vocab < 2 * nb:
+            raise ValueError('the vocabulary must hold 2 * num_beams candidates')
+        from . import gpt2_decode
+        if not gpt2_decode.session_usable(self, enc.shape[1], need_graph=False):
+            raise NotImplementedError('num_beams, length_penalty, early_stopping and logits processors on a beam search need the device route '
+                                      'of the distilgpt2 search: there is no host-driven route for them')
+        opts = dict(repetition_penalty=o['repetition_penalty'], no_repeat_ngram_size=o['no_repeat_ngram_size'], min_length=o['min_length'],
+                    length_penalty=bc['length_penalty'], early_stopping=bc['early_stopping'])
+        return gpt2_decode.search(self, enc, n, return_scores, step_hook, slot, as_iterator, burst, nb=nb, opts=opts)
+
     def _generate_processed(self, enc, o, num_return_sequences, return_scores, return_logprobs, step_hook, slot, as_iterator, burst, uniforms,
                             generator):
         """generate() with do_sample or a logits processor switched on: the device session of gpt2_decode.sample"""
         if int(self.beam_size) != 1:
-            raise NotImplementedError('sampling and logits processors need beam_size 1 (beam search with processors is not built), not %d'
-                                      % int(self.beam_size))
+            raise NotImplementedError('sampling and logits processors need beam_size 1, not %d (a beam search takes repetition_penalty, '
+                                      'no_repeat_ngram_size and min_length once num_beams is given)' % int(self.beam_size))
         n = self.sample_n if num_return_sequences is None else int(num_return_sequences)
         if n < 1 or (n > 1 and not o['do_sample']):
             raise ValueError('num_return_sequences must be >= 1, and 1 without do_sample, not %d' % n)

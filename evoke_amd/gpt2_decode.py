@@ -12,7 +12,11 @@ The session (caches, row table, cross K / V, hypothesis arrays, captured step, r
 batch of its geometry; decode._Session._drive supplies warm-up, capture, replay and burst yields.
 
 _GPT2SampleSession is the same for Hugging Face's sampling / greedy decoding with logits processors (num_beams 1): the same GPT-2 step
-without the log_softmax, and evk_hf_sample_step (csrc/hf_sample.hip) on the raw logits in place of evk_hf_beam_step."""
+without the log_softmax, and evk_hf_sample_step (csrc/hf_sample.hip) on the raw logits in place of evk_hf_beam_step.
+
+_GPT2BeamOptionsSession is the beam session with Hugging Face's repetition_penalty / no_repeat_ngram_size / min_length processors on the
+log-probability rows and the scorer's length_penalty / early_stopping: the same captured step with evk_hf_beam_step_opts as its bookkeeping
+launch -- one launch still, so a step keeps the plain beam step's launch count."""
 import ctypes as C
 import math
 from collections import deque
@@ -55,6 +59,7 @@ def _attend(q, ldq, k, v, knew, vnew, rowmap, last_pos, R, S, heads, dh, kv_div)
 class _GPT2Session(decode._Session):
     """The session of a distilgpt2 beam search over B studies x nb beams: self-attention caches and their row table, cross-attention K / V,
     the log-probability buffer, position counter and ticket, the running beams and the hypothesis lists of evk_hf_beam_step."""
+    route = 'beam'                       # what decode.stats['gpt2_route'] reports
 
     def __init__(self, dec, B, nb, max_len, S, dev, slot=0, n_return=1):
         # (decode._Session.__init__ sizes its buffers from the R2Gen model: this backend allocates its own and shares the driving code)
@@ -197,11 +202,44 @@ class _GPT2Session(decode._Session):
         self._book(True)                                                 # the last position: every study that is not done closes its beams
         decode._reap_plans()
         decode.stats['gpt2_steps_issued'] = self.issued + 1
-        decode.stats['gpt2_route'] = 'beam'
+        decode.stats['gpt2_route'] = self.route
         packed = torch.cat([self.hyp_seq[:, :n].reshape(B * n, max_len), self.hyp_len[:, :n].reshape(B * n, 1).long()], dim=1)
         if return_scores:
             return packed, self.hyp_score[:, :n].reshape(-1).clone()
         return packed
+
+
+BEAM_NEUTRAL = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, length_penalty=1.0, early_stopping=False)
+
+
+def length_divisors(length_penalty, max_len):
+    """D[c] = c ** length_penalty for c = 0 .. max_len as Python floats (what HF's scorer divides a sum by at cur_len = c; D[0] is never
+    read): computed here and handed to the kernel as f64, so that a score is the quotient a host restatement computes"""
+    lp = float(length_penalty)
+    return [(float(c) ** lp) if c or lp >= 0 else float('inf') for c in range(max_len + 1)]
+
+
+class _GPT2BeamOptionsSession(_GPT2Session):
+    """_GPT2Session whose bookkeeping launch is evk_hf_beam_step_opts: the three logits processors on the running beams' rows (in place
+    in logp_buf, which log_softmax rewrites every step) and the scorer's length_penalty / early_stopping.  The options are kernel arguments
+    of the captured step, so they are part of the session's key (see search()).  Everything else is the beam session's."""
+    route = 'beam-options'
+
+    def __init__(self, dec, B, nb, max_len, S, dev, opts, slot=0, n_return=1):
+        super().__init__(dec, B, nb, max_len, S, dev, slot, n_return)
+        self.opts = dict(opts)
+        lp = float(self.opts['length_penalty'])
+        self.len_div = None if lp == 1.0 else torch.tensor(length_divisors(lp, max_len), dtype=torch.float64, device=dev)
+
+    def _book(self, last):
+        dec, o = self.dec, self.opts
+        H.check(H.lib.evk_hf_beam_step_opts(H.ptr(self.logp_buf), self.logp_buf.stride(0), self.V, self.nb, self.B, self.max_len, H.ptr(self.pos),
+                                            dec.eos_token_id, dec.pad_token_id, int(last), H.ptr(self.scores), H.ptr(self.seqs),
+                                            H.ptr(self.words), H.ptr(self.anc), self.anc.shape[1], H.ptr(self.hyp_score), H.ptr(self.hyp_len),
+                                            H.ptr(self.hyp_seq), H.ptr(self.done), H.ptr(self.n_done), None if last else H.ptr(self.pos),
+                                            H.ptr(self.ticket), C.c_float(o['repetition_penalty']), int(o['no_repeat_ngram_size']),
+                                            int(o['min_length']), H.ptr(self.len_div) if self.len_div is not None else None,
+                                            int(bool(o['early_stopping'])), H.stream()), 'hf_beam_step_opts')
 
 
 class _GPT2SampleSession(_GPT2Session):
@@ -311,13 +349,18 @@ def unpack(packed, host=None):
     return packed[:, :L]
 
 
-def search(dec, enc, n_return, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0):
-    """the device route of DistilGPT2TextDecoderModel.generate; as_iterator: a generator that yields after every issued step and returns
-    the PACKED result (see _run_iter / unpack)"""
+def search(dec, enc, n_return, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, nb=None, opts=None):
+    """the device route of DistilGPT2TextDecoderModel.generate at width nb (default: the decoder's beam_size); opts: the beam options
+    resolved and validated by generate (keys of BEAM_NEUTRAL) -- None or all neutral: the plain beam session; as_iterator: a generator that
+    yields after every issued step and returns the PACKED result (see _run_iter / unpack)"""
     B, S, dev = enc.shape[0], enc.shape[1], enc.device
-    nb, max_len = int(dec.beam_size), int(dec.max_seq_len)
-    key = ('gpt2', B, nb, max_len, S, dev.index, slot, n_return)
-    ses = decode._session_for(dec, key, lambda: _GPT2Session(dec, B, nb, max_len, S, dev, slot, n_return))
+    nb, max_len = int(dec.beam_size if nb is None else nb), int(dec.max_seq_len)
+    if opts is None or dict(opts) == BEAM_NEUTRAL:
+        key = ('gpt2', B, nb, max_len, S, dev.index, slot, n_return)
+        ses = decode._session_for(dec, key, lambda: _GPT2Session(dec, B, nb, max_len, S, dev, slot, n_return))
+    else:
+        key = ('gpt2-beam-options', B, nb, max_len, S, dev.index, slot, n_return, tuple(sorted(opts.items())))
+        ses = decode._session_for(dec, key, lambda: _GPT2BeamOptionsSession(dec, B, nb, max_len, S, dev, opts, slot, n_return))
     enc = enc.contiguous()
     if as_iterator:
         return ses.run_iter(enc, return_scores, step_hook, burst)

@@ -530,6 +530,23 @@ int evk_hf_beam_step(const float* logp, int32_t ld, int32_t V, int32_t nb, int32
                      int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
                      double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
                      int32_t* ticket, evk_stream_t stream);
+/* evk_hf_beam_step with what Hugging Face's `generate` adds to a beam search on request (same kernel body, hf_beam.hip).  cur_len = *pos + 1
+ * ids so far, [BOS] included.  For every study that is not done, on the f32 log-probability row of each of its nb running beams, from that
+ * beam's own history seqs[b*nb+j][0 .. cur_len-1], IN PLACE in logp (columns V .. ld-1 and the rows of a done study are neither read nor
+ * written), in HF's order:
+ *   repetition_penalty rp > 0 (1 = off): every distinct id w of the history once ([BOS] / [PAD] included), x[w] = x[w] < 0 ? x[w] * rp : x[w] / rp;
+ *   no_repeat_ngram_size g in [0, 8] (0 = off): if cur_len >= g, every earlier window of g ids whose first g-1 ids equal the last g-1 ids of
+ *   the history bans its own last id, x[w] = -inf (g = 1 bans every id present; a ban wins over a penalty);
+ *   min_length: cur_len < min_length -> x[eos] = -inf.
+ * Then the search of evk_hf_beam_step with two changes: a hypothesis score is (double)sum / D[cur_len], D = len_div, a device table of
+ * max_len + 1 doubles (cur_len ** length_penalty, computed by the caller; NULL: D[c] = c), and a study is done when its list is full and
+ * (early_stopping != 0 or hyp_score[nb-1] >= (double)(rank-0 candidate) / D[cur_len]).
+ * With rp 1, g 0, min_length 0, len_div NULL and early_stopping 0 every array receives the bits evk_hf_beam_step writes. */
+int evk_hf_beam_step_opts(float* logp, int32_t ld, int32_t V, int32_t nb, int32_t B, int32_t max_len, const int64_t* pos, int32_t eos,
+                          int32_t pad, int32_t force_end, float* scores, int64_t* seqs, int64_t* words, int32_t* anc, int32_t anc_cols,
+                          double* hyp_score, int32_t* hyp_len, int64_t* hyp_seq, unsigned char* done, int32_t* n_done, int64_t* pos_advance,
+                          int32_t* ticket, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const double* len_div,
+                          int32_t early_stopping, evk_stream_t stream);
 /* One launch for everything AttModel._sample does between two decoder steps (sample.hip; modules/att_model.py:176-221 and
  * CaptionModel.sample_next_word, modules/caption_model.py:363-401), for R independent rows.  logp [R][ld] f32 log-probs (V1 = V+1 valid
  * columns, V1 <= 4096); *pos = position t being written.  In the reference's order: decoding_constraint != 0 and t > 0: column seq[r][t-1]

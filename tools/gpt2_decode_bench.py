@@ -7,8 +7,13 @@ captured step.  Uses only the public generate(), so the same file measures a com
 --do-sample / --top-k / --top-p / --repetition-penalty time the sampling route (gpt2_decode._GPT2SampleSession, --beam 1) instead; the
 uniform numbers are drawn once, outside the timed calls, so that every run draws the same reports.
 
+--num-beams / --no-repeat-ngram-size / --min-length / --length-penalty / --early-stopping time the beam search with options
+(gpt2_decode._GPT2BeamOptionsSession; --repetition-penalty joins them once one of them is given).  Without them the call carries no new
+keyword, so the same file still measures a commit from before them.
+
     python tools/gpt2_decode_bench.py [--studies 32] [--beam 3] [--max-seq-len 100] [--runs 3]
-                                      [--do-sample] [--top-k K] [--top-p P] [--repetition-penalty RP]"""
+                                      [--do-sample] [--top-k K] [--top-p P] [--repetition-penalty RP]
+                                      [--num-beams N] [--no-repeat-ngram-size G] [--min-length M] [--length-penalty LP] [--early-stopping]"""
 import argparse
 import json
 import os
@@ -31,6 +36,11 @@ def main():
     ap.add_argument('--top-k', type=int, default=0)
     ap.add_argument('--top-p', type=float, default=1.0)
     ap.add_argument('--repetition-penalty', type=float, default=1.0)
+    ap.add_argument('--num-beams', type=int, default=None)
+    ap.add_argument('--no-repeat-ngram-size', type=int, default=0)
+    ap.add_argument('--min-length', type=int, default=0)
+    ap.add_argument('--length-penalty', type=float, default=None)
+    ap.add_argument('--early-stopping', action='store_true')
     a = ap.parse_args()
     from evoke_amd import decode, ops
     from evoke_amd.config import ARGS
@@ -53,6 +63,11 @@ def main():
         kw = dict(do_sample=a.do_sample, top_k=a.top_k, top_p=a.top_p, repetition_penalty=a.repetition_penalty)
         if a.do_sample:
             kw['uniforms'] = torch.rand(a.studies, a.max_seq_len, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1))
+    if a.num_beams is not None or a.no_repeat_ngram_size or a.min_length or a.length_penalty is not None or a.early_stopping:
+        # the beam search with options: the width is given explicitly, which is what takes generate() to that route
+        kw = dict(num_beams=a.num_beams if a.num_beams is not None else a.beam, repetition_penalty=a.repetition_penalty,
+                  no_repeat_ngram_size=a.no_repeat_ngram_size, min_length=a.min_length, early_stopping=a.early_stopping,
+                  length_penalty=a.length_penalty if a.length_penalty is not None else 1.0)
     runs = []
     for i in range(2 + a.runs):
         decode.stats.pop('step_events', None)
