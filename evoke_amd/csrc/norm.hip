@@ -600,6 +600,123 @@ int launch_decode_attn(const DecAttP& p, hipStream_t s) {
   return evk_check_launch("decode_attention");
 }
 
+// ------------------------------------------------------------------------------------------------
+// decode_attn_kernel for the cross attention of a search that returns its attention maps (evk_decode_attention_maps): the same arithmetic
+// on q, K, V in the same order -- `out` gets the same bits -- and, from the same launch, the head-mean probabilities of every row
+// (MultiHeadedAttention.attn, encoder_decoder.py:189,200, averaged over the heads).  A kernel of its own and not a template of the one
+// above: the cross attention has no row table, no position limit and no fused append, and the kernel above keeps its code to the
+// instruction.  One workgroup owns ALL heads of row r, four at a time (wave wv takes head h0 + wv).  The online softmax knows its max and
+// sum only at the end, so the scaled scores of a head stay in LDS (4 x 256 floats) and are normalised with the final (mrun, lrun): masked
+// keys give exactly 0, a row without keys a row of zeros.  Thread s then sums key s over the heads in the order h = 0 .. H-1: no atomics,
+// the same bits at every launch.  (The beams of a sample no longer share a workgroup, so their K / V lines meet in L2, not in the CU's L1.)
+// ------------------------------------------------------------------------------------------------
+struct DecAttMaps { float* maps; long maps_ld; const long long* slab_pos; long slab_stride; };
+
+__global__ __launch_bounds__(256) void decode_attn_maps_kernel(const DecAttP p, const DecAttMaps m) {
+  __shared__ float sp[4][256];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = blockIdx.x;
+  const int g = lane >> 3, c = lane & 7;
+  const long HD = (long)p.H * 64;
+  const long rk = r / p.kv_div;
+  const unsigned char* mk = p.mask ? p.mask + rk * p.S : nullptr;
+  const int passes = (p.S + 7) >> 3;
+  constexpr int UNR = EVK_DEC_ATTN_UNR;
+  float acc = 0.f;                                  // thread s: sum over the heads of the probability of key s
+  for (int h0 = 0; h0 < p.H; h0 += 4) {
+    const int h = h0 + wv;
+    if (h < p.H) {
+      float qr[8];
+      {
+        const uint4 u = *reinterpret_cast<const uint4*>(p.q + (long)r * HD + h * 64 + c * 8);
+        qr[0] = lo_bf(u.x); qr[1] = hi_bf(u.x); qr[2] = lo_bf(u.y); qr[3] = hi_bf(u.y);
+        qr[4] = lo_bf(u.z); qr[5] = hi_bf(u.z); qr[6] = lo_bf(u.w); qr[7] = hi_bf(u.w);
+      }
+      const bf16_t* kb = p.k + rk * p.S * HD + h * 64 + c * 8;
+      const bf16_t* vb = p.v + rk * p.S * HD + h * 64 + c * 8;
+      float mrun = -INFINITY, lrun = 0.f;
+      float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int it0 = 0; it0 < passes; it0 += UNR) {
+        uint4 ku[UNR], vu[UNR];
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+          const int s = (it0 + j) * 8 + g;
+          const bool ok = s < p.S;
+          const long off = ok ? (long)s * HD : 0;
+          ku[j] = ok ? *reinterpret_cast<const uint4*>(kb + off) : make_uint4(0, 0, 0, 0);
+          vu[j] = ok ? *reinterpret_cast<const uint4*>(vb + off) : make_uint4(0, 0, 0, 0);
+        }
+        float sc[UNR];
+        float bmax = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+          const int s = (it0 + j) * 8 + g;
+          const uint4 u = ku[j];
+          float a = lo_bf(u.x) * qr[0] + hi_bf(u.x) * qr[1] + lo_bf(u.y) * qr[2] + hi_bf(u.y) * qr[3] + lo_bf(u.z) * qr[4] + hi_bf(u.z) * qr[5] +
+                    lo_bf(u.w) * qr[6] + hi_bf(u.w) * qr[7];
+          a += __shfl_xor(a, 1, 64);
+          a += __shfl_xor(a, 2, 64);
+          a += __shfl_xor(a, 4, 64);
+          sc[j] = (s < p.S && !(mk && !mk[s])) ? a * p.scale : -INFINITY;
+          if (c == 0 && s < p.S) sp[wv][s] = sc[j];
+          bmax = fmaxf(bmax, sc[j]);
+        }
+        bmax = fmaxf(bmax, __shfl_xor(bmax, 8, 64));
+        bmax = fmaxf(bmax, __shfl_xor(bmax, 16, 64));
+        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
+        const float mnew = fmaxf(mrun, bmax);
+        const float resc = (mrun == -INFINITY) ? 0.f : __expf(mrun - mnew);
+        lrun *= resc;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] *= resc;
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+          const float e = (sc[j] == -INFINITY || mnew == -INFINITY) ? 0.f : __expf(sc[j] - mnew);
+          lrun += e;
+          const uint4 u = vu[j];
+          o[0] += e * lo_bf(u.x); o[1] += e * hi_bf(u.x); o[2] += e * lo_bf(u.y); o[3] += e * hi_bf(u.y);
+          o[4] += e * lo_bf(u.z); o[5] += e * hi_bf(u.z); o[6] += e * lo_bf(u.w); o[7] += e * hi_bf(u.w);
+        }
+        mrun = mnew;
+      }
+      lrun += __shfl_xor(lrun, 8, 64);
+      lrun += __shfl_xor(lrun, 16, 64);
+      lrun += __shfl_xor(lrun, 32, 64);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        o[j] += __shfl_xor(o[j], 8, 64);
+        o[j] += __shfl_xor(o[j], 16, 64);
+        o[j] += __shfl_xor(o[j], 32, 64);
+      }
+      const float inv = lrun > 0.f ? 1.f / lrun : 0.f;
+      if (g == 0) {
+        *reinterpret_cast<uint4*>(p.out + (long)r * HD + h * 64 + c * 8) =
+            make_uint4(pack2bf(o[0] * inv, o[1] * inv), pack2bf(o[2] * inv, o[3] * inv), pack2bf(o[4] * inv, o[5] * inv), pack2bf(o[6] * inv, o[7] * inv));
+      }
+      // the probabilities of this head, in place of its scores (written by the c == 0 lanes of this wave)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int s = lane; s < p.S; s += 64) {
+        const float x = sp[wv][s];
+        sp[wv][s] = x == -INFINITY ? 0.f : __expf(x - mrun) * inv;
+      }
+    }
+    __syncthreads();
+    const int s = threadIdx.x;
+    if (s < p.S)
+      for (int j = 0; j < 4 && h0 + j < p.H; ++j) acc += sp[j][s];
+    __syncthreads();
+  }
+  const int s = threadIdx.x;
+  if (s < p.S) m.maps[(m.slab_pos ? (long)*m.slab_pos : 0) * m.slab_stride + (long)r * m.maps_ld + s] = acc * (1.f / (float)p.H);
+}
+
+int launch_decode_attn_maps(const DecAttP& p, const DecAttMaps& m, hipStream_t s) {
+  hipLaunchKernelGGL(decode_attn_maps_kernel, dim3(p.R), dim3(256), 0, s, p, m);
+  return evk_check_launch("decode_attention_maps");
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,6 +862,20 @@ int evk_decode_attention(const void* q, const void* k, const void* v, const unsi
   DecAttP p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, mask, (bf16_t*)out, R, S, heads, kv_div, scale, nullptr, nullptr, nullptr, nullptr, 0};
   ProfScope ps(EVK_FAM_NORM, s);
   return launch_decode_attn(p, s);
+}
+
+int evk_decode_attention_maps(const void* q, const void* k, const void* v, const unsigned char* mask, void* out, float* maps, int64_t maps_ld,
+                              const int64_t* slab_pos, int64_t slab_stride, int32_t R, int32_t S, int32_t heads, int32_t dh, int32_t kv_div,
+                              float scale, evk_stream_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EVK_REQUIRE(q && k && v && out && maps && R > 0 && heads > 0, "decode_attention_maps: null/empty");
+  EVK_REQUIRE(dh == 64 && S >= 1 && S <= 256, "decode_attention_maps: head_dim must be 64 and 1 <= S <= 256 (got %d, %d)", dh, S);
+  EVK_REQUIRE(kv_div >= 1 && R % kv_div == 0, "decode_attention_maps: R=%d must be a multiple of kv_div=%d", R, kv_div);
+  EVK_REQUIRE(maps_ld >= S && slab_stride >= 0, "decode_attention_maps: maps_ld=%lld must hold a row of S=%d", (long long)maps_ld, S);
+  DecAttP p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, mask, (bf16_t*)out, R, S, heads, kv_div, scale, nullptr, nullptr, nullptr, nullptr, 0};
+  DecAttMaps m{maps, (long)maps_ld, reinterpret_cast<const long long*>(slab_pos), (long)slab_stride};
+  ProfScope ps(EVK_FAM_NORM, s);
+  return launch_decode_attn_maps(p, m, s);
 }
 
 int evk_decode_attention_indirect(const void* q, const void* k, const void* v, const unsigned char* mask, const int32_t* rowmap,

@@ -227,6 +227,10 @@ class _DecoderState:
             self.rows = torch.arange(R, dtype=torch.int32, device=enc.device).view(R, 1)
             self.anc = self.rows.expand(R, max_len).contiguous()
         self.logit_scale = 1.0           # 1 / temperature of the beam search's later steps (step_static only; caption_model.py:196)
+        # cross-attention map history f32 [positions][R][n_layers * S] of a search that returns its maps (set by the session), or None: the
+        # step then writes, from the cross-attention launch itself, layer i's head-mean probabilities of every row into columns
+        # [i * S, (i + 1) * S) of the slab of the position it computes (evk_decode_attention_maps)
+        self.maps = None
         self.tmem = None                 # tanh(memory), kept beside the memory by the session path (evk_rm_decode_step)
         # the f32 relational memory (evk_rm_decode_step_f32): the state, the unrounded token embedding, scratch, the 16-bit row for the decoder
         self.mem32 = self.emb32 = self.rm32_ws = self.rm32_out = None
@@ -296,12 +300,25 @@ class _DecoderState:
                                                H.stream()), 'decode_attention_qkv')
         return c
 
+    def _cross_attend(self, i, q, pos=None):
+        """cross-attention of layer i for the queries q (R, 1, d) -> (R, 1, d).  With a map history (self.maps) the same launch also writes
+        the rows' head-mean probabilities into the slab of position *pos (a device scalar; None: slab 0)."""
+        h = self.model.decoder.layers[0].self_attn.h
+        if self.maps is None:
+            return _attend1(q, self.kc[i], self.vc[i], h, self.src_mask)
+        R = q.shape[0]
+        Rk, S, HD = self.kc[i].shape
+        out = torch.empty_like(q)
+        H.check(H.lib.evk_decode_attention_maps(H.ptr(q), H.ptr(self.kc[i]), H.ptr(self.vc[i]), H.ptr(self.src_mask), H.ptr(out),
+                                                self.maps.data_ptr() + 4 * i * S, self.maps.shape[-1], H.ptr(pos), self.maps.stride(0), R, S, h,
+                                                HD // h, R // Rk, C.c_float(1.0 / math.sqrt(HD // h)), H.stream()), 'decode_attention_maps')
+        return out
+
     def step_static(self, it, pos, out=None, seed_rows=True):
         """step() with the position held in a device tensor `pos` (1,) and self-attention over the cache row table (positions <= *pos,
         read from the device): no host-side shape depends on the step index, so the launch sequence can be captured once in a HIP graph
         and replayed.  Needs a state built with row_table=True."""
         model = self.model
-        h = model.decoder.layers[0].self_attn.h
         if seed_rows:
             self.anc.index_copy_(1, pos, self.rows)      # this step's K / V are written to the hypothesis's own cache row
         # the positional row is picked on the device (pos is a device scalar inside the captured step)
@@ -340,7 +357,7 @@ class _DecoderState:
                 c = self._self_attend(i, fw.qkv(i, n), pos)
                 x, n = fw.rowblock(c.view(-1, d), x, w['so'], w['so_b'], 3 * i + 1, deltas, sync=self.rb_sync)
                 q = layer.src_attn.linears[0](n)
-                c = _attend1(q.view(-1, 1, d), self.kc[i], self.vc[i], h, self.src_mask)
+                c = self._cross_attend(i, q.view(-1, 1, d), pos)
                 x, n = fw.rowblock(c.view(-1, d), x, w['co'], w['co_b'], 3 * i + 2, deltas, sync=self.rb_sync)
                 x, n = fw.rowblock(n, x, w['w2'], w['b2'], 3 * (i + 1) if i + 1 < nl else None, deltas, w1=w['w1'], b1=w['b1'], sync=self.rb_sync)
         else:
@@ -350,7 +367,7 @@ class _DecoderState:
                 x = layer.self_attn.linears[3](c.view(-1, d), resid=x)
                 ca = layer.src_attn
                 q = ca.linears[0](fw.norm(3 * i + 1, x, deltas))
-                c = _attend1(q.view(-1, 1, d), self.kc[i], self.vc[i], h, self.src_mask)
+                c = self._cross_attend(i, q.view(-1, 1, d), pos)
                 x = ca.linears[3](c.view(-1, d), resid=x)
                 x = layer.feed_forward(fw.norm(3 * i + 2, x, deltas), resid=x)
             n = model.decoder.norm(x).view(-1, d)
@@ -384,7 +401,10 @@ class _DecoderState:
             x = sa.linears[3](c, resid=x)
             n = layer.sublayer[1].norm(x, memory)
             ca = layer.src_attn
-            c = ops.attention(ca.linears[0](n), self.kc[i], self.vc[i], h, mask=self.src_mask)
+            if self.maps is None:
+                c = ops.attention(ca.linears[0](n), self.kc[i], self.vc[i], h, mask=self.src_mask)
+            else:
+                c = self._cross_attend(i, ca.linears[0](n).contiguous())      # (a one-position state: slab 0)
             x = ca.linears[3](c, resid=x)
             n = layer.sublayer[2].norm(x, memory)
             x = layer.feed_forward(n, resid=x)
@@ -614,10 +634,11 @@ def _length_divisors(length_penalty, max_len):
     return [((5 + t) ** alpha) / ((5 + 1) ** alpha) for t in range(1, max_len + 1)]
 
 
-def beam_options(args, beam, return_logprobs=False):
+def beam_options(args, beam, return_logprobs=False, return_attention=False):
     """The options of CaptionModel.beam_search / AttModel._sample_beam read from `args` and validated -> None when every one is at its
-    default and no log-probabilities are asked for (the search then runs exactly the launches it always ran), else a dict (part of the
-    session key: the options are kernel arguments of the captured step)."""
+    default and neither log-probabilities nor attention maps are asked for (the search then runs exactly the launches it always ran), else a
+    dict (part of the session key: the options are kernel arguments of the captured step).  `return_attention` is an entry of the dict only
+    when set, so the keys of every other search stay what they were."""
     if args.get('group_size', 1) != 1:
         raise NotImplementedError("diverse beam search (group_size > 1) is not on the path: the reference's own grouped search fails "
                                   '(CaptionModel.beam_search calls self.repeat_tensor, which no class defines), so there is nothing to match')
@@ -635,7 +656,9 @@ def beam_options(args, beam, return_logprobs=False):
     _length_divisors(length_penalty, 1)
     opts = dict(temperature=temperature, decoding_constraint=int(bool(args.get('decoding_constraint', 0))), length_penalty=str(length_penalty),
                 sample_n=n, return_logprobs=bool(return_logprobs))
-    if opts == dict(temperature=1.0, decoding_constraint=0, length_penalty='', sample_n=1, return_logprobs=False):
+    if return_attention:
+        opts['return_attention'] = True
+    elif opts == dict(temperature=1.0, decoding_constraint=0, length_penalty='', sample_n=1, return_logprobs=False):
         return None
     return opts
 
@@ -645,7 +668,7 @@ class _BeamLists:
     words, and per position the row whose log-probabilities scored it), the length-penalty table, and -- only when log-probabilities are
     asked for -- the history of every step's rows (max_len x R x (V+1) f32: ~225 MB at 32 studies x beam 4 x 100 positions x 4.4 k words)."""
 
-    def __init__(self, dec, B, beam, max_len, dev, opts):
+    def __init__(self, dec, B, beam, max_len, dev, opts, S=0):
         self.dec, self.B, self.beam, self.max_len, self.opts = dec, B, beam, max_len, opts
         self.score = torch.empty(B, beam, dtype=torch.float64, device=dev)
         self.len = torch.empty(B, beam, dtype=torch.int32, device=dev)
@@ -654,6 +677,10 @@ class _BeamLists:
         div = _length_divisors(opts['length_penalty'], max_len)
         self.len_div = torch.tensor(div, dtype=torch.float64, device=dev) if div is not None else None
         self.hist = torch.empty(max_len, B * beam, dec.vocab_size + 1, dtype=F32, device=dev) if opts['return_logprobs'] else None
+        # the cross-attention maps of every step's rows, indexed like hist (slab t = the step that computed position t, so `anc` names the
+        # row): max_len x R x (n_layers * S) f32, 22 MB at 32 studies x beam 4 x 100 positions x 3 layers x 144 patch tokens
+        self.nl = len(dec.model.decoder.layers)
+        self.hist_attn = torch.zeros(max_len, B * beam, self.nl * S, dtype=F32, device=dev) if opts.get('return_attention') else None
 
     def reset(self):
         self.score.fill_(-float('inf'))
@@ -662,8 +689,8 @@ class _BeamLists:
         self.anc.zero_()
 
     def result(self, return_scores):
-        """-> seq (rows, max_len) [, seq_logprobs (rows, max_len, V+1) f32] [, scores (rows,) f64], rows = B * sample_n, the entries of a
-        study next to each other in list order (att_model.py:126-135)"""
+        """-> seq (rows, max_len) [, seq_logprobs (rows, max_len, V+1) f32] [, attention (rows, max_len, n_layers, S) f32] [, scores (rows,)
+        f64], rows = B * sample_n, the entries of a study next to each other in list order (att_model.py:126-135)"""
         n, B, max_len, V1 = self.opts['sample_n'], self.B, self.max_len, self.dec.vocab_size + 1
         out = [self.seq[:, :n].reshape(B * n, max_len).clone()]
         if self.hist is not None:
@@ -671,6 +698,13 @@ class _BeamLists:
             H.check(H.lib.evk_beam_gather_logprobs(H.ptr(self.hist), H.ptr(self.anc), H.ptr(self.len), H.ptr(slp), B, self.beam, n, max_len, V1,
                                                    H.stream()), 'beam_gather_logprobs')
             out.append(slp)
+        if self.hist_attn is not None:
+            # the same gather with n_layers * S columns: row t of an entry comes from the row that scored its word t
+            W = self.hist_attn.shape[-1]
+            att = torch.empty(B * n, max_len, W, dtype=F32, device=self.seq.device)
+            H.check(H.lib.evk_beam_gather_logprobs(H.ptr(self.hist_attn), H.ptr(self.anc), H.ptr(self.len), H.ptr(att), B, self.beam, n, max_len, W,
+                                                   H.stream()), 'beam_gather_logprobs')
+            out.append(att.view(B * n, max_len, self.nl, W // self.nl))
         if return_scores:
             out.append(self.score[:, :n].reshape(-1).clone())
         return out[0] if len(out) == 1 else tuple(out)
@@ -734,7 +768,10 @@ class _BeamSession(_Session):
     def __init__(self, dec, B, beam, max_len, S, dev, slot=0, opts=None):
         super().__init__(dec, B, B * beam, max_len, S, dev, slot)
         self.beam = beam
-        self.lists = _BeamLists(dec, B, beam, max_len, dev, opts) if opts is not None else None
+        self.lists = _BeamLists(dec, B, beam, max_len, dev, opts, S) if opts is not None else None
+        self.hist_attn = self.lists.hist_attn if self.lists is not None else None
+        # position 0 runs for B rows (st0): its maps land here and go to slab 0 once per beam
+        self.maps0 = torch.empty(1, B, self.hist_attn.shape[-1], dtype=F32, device=dev) if self.hist_attn is not None else None
         self.beam_seq = torch.zeros(B, beam, max_len, dtype=torch.long, device=dev)
         self.beam_sum = torch.zeros(B, beam, dtype=F32, device=dev)
         self.best_p = torch.empty(B, dtype=F32, device=dev)
@@ -769,7 +806,11 @@ class _BeamSession(_Session):
         st = self.st
         # ---- position 0: B rows, eagerly (modules/att_model.py:118-124: one decoder call with [BOS], then the features are tiled x beam)
         st0 = _DecoderState(dec, enc, src_mask, 1, cross_kv=(self.kc, self.vc))
+        st.maps, st0.maps = self.hist_attn, self.maps0
         logp0 = st0.step(torch.full((B,), dec.bos_idx, dtype=torch.long, device=dev))            # (B, V+1)
+        if self.hist_attn is not None:
+            # every source row of position 0 is the study's one row, as _beam_first_position arranges the log-probability rows
+            self.hist_attn[0].copy_(self.maps0[0].repeat_interleave(beam, 0))
         self.beam_seq.zero_()
         self.beam_sum.zero_()
         self.best_p.fill_(-float('inf'))
@@ -821,9 +862,12 @@ class _SampleSession(_Session):
     places, so neither the caches nor the memory are permuted) plus the arrays of csrc/sample.hip.  The options are kernel arguments of the
     captured step, so they are part of the session's key (see sample())."""
 
-    def __init__(self, dec, B, n, max_len, S, dev, opts, return_logprobs, slot=0):
+    def __init__(self, dec, B, n, max_len, S, dev, opts, return_logprobs, slot=0, return_attention=False):
         super().__init__(dec, B, B * n, max_len, S, dev, slot)
         R, V1 = self.R, dec.vocab_size + 1
+        self.nl = len(dec.model.decoder.layers)
+        # the cross-attention maps of every step, slab t written by the step that computes position t (rows never trade places here)
+        self.hist_attn = torch.zeros(max_len, R, self.nl * S, dtype=F32, device=dev) if return_attention else None
         self.opts = opts
         self.seq = torch.empty(R, max_len, dtype=torch.long, device=dev)
         self.unfinished = torch.empty(R, dtype=torch.uint8, device=dev)
@@ -843,11 +887,12 @@ class _SampleSession(_Session):
         self.st.step_static(self.words, self.pos, out=self.logp_buf, seed_rows=False)
 
     def _run_iter(self, enc, src_mask, uniforms=None, step_hook=None, burst=0):
-        """as _BeamSession._run_iter (same yields, same burst protocol) -> (seq, seq_logprobs or None)"""
+        """as _BeamSession._run_iter (same yields, same burst protocol) -> (seq, seq_logprobs or None [, attention])"""
         dec, max_len = self.dec, self.max_len
         hook = step_hook if step_hook is not None else (lambda *a: None)
         self._refill(enc, src_mask)
         st = self.st
+        st.maps = self.hist_attn
         # ---- every row starts from the initial memory and [BOS] at position 0 (att_model.py:157-173)
         if self.mem0 is None or self.mem0.shape != st.mem.shape:
             self.mem0 = dec.model.rm.init_memory(self.R, enc.device).to(st.mem.dtype).contiguous()
@@ -874,7 +919,14 @@ class _SampleSession(_Session):
         yield from self._drive(max_len - 1, 1, step_hook, burst)
         self._book_kernel(True)                                               # the last position: nothing follows it
         _reap_plans()
-        return self.seq.clone(), (self.seq_logprobs.clone() if self.seq_logprobs is not None else None)
+        out = (self.seq.clone(), (self.seq_logprobs.clone() if self.seq_logprobs is not None else None))
+        if self.hist_attn is not None:
+            # the history transposed to rows first; a row that has emitted [EOS] (or [PAD]) keeps stepping: its later maps are zeroed
+            ended = (self.seq == dec.eos_idx) | (self.seq == dec.pad_idx)
+            live = (ended.cumsum(1) - ended.long()) == 0                       # no end mark in front of position t
+            att = self.hist_attn.permute(1, 0, 2).reshape(self.R, max_len, self.nl, -1)
+            out = out + (att * live.view(self.R, max_len, 1, 1).to(F32),)
+        return out
 
 
 def _sample_step(dec, logp, pos, seq, unfinished, words, seq_logprobs, uniforms, opts, block_rows, pos_advance, ticket):
@@ -895,6 +947,24 @@ def _session_ok(dec, args):
     return _SESSION[0] and model.d_model // h == 64 and int(args['max_seq_len']) <= 256
 
 
+def _attention_ok(dec, args, S):
+    """attention maps come out of the session's cross-attention kernel (evk_decode_attention_maps): refuse, with the reason, what it does not
+    serve"""
+    model = dec.model
+    h = model.decoder.layers[0].self_attn.h
+    why = None
+    if not _SESSION[0]:
+        why = 'the decode session is switched off (EVK_DECODE_SESSION=0)'
+    elif model.d_model // h != 64:
+        why = 'the head size is %d, the kernel serves 64' % (model.d_model // h)
+    elif int(args['max_seq_len']) > 256:
+        why = 'max_seq_len %d exceeds the 256 positions of the session' % int(args['max_seq_len'])
+    elif S > 256:
+        why = '%d encoder tokens exceed the 256 keys of the kernel' % S
+    if why is not None:
+        raise NotImplementedError('return_attention needs the decode session and its cross-attention kernel: ' + why)
+
+
 def _session_for(dec, key, make):
     """the decoder's session under `key`, built by make() on first use.  A few batch geometries / slots at most (each holds its caches:
     6 x R x max_len x 512 x 2 B), the least recently used evicted first.  A generator still in flight keeps its evicted session alive, whose
@@ -910,7 +980,8 @@ def _session_for(dec, key, make):
 
 
 @torch.no_grad()
-def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, return_logprobs=False):
+def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=None, slot=0, as_iterator=False, burst=0, return_logprobs=False,
+                return_attention=False):
     """AttModel._sample_beam (modules/att_model.py:98-137) -> seq (rows, max_seq_len) int64 token ids padded with [PAD]; with return_logprobs
     (seq, seq_logprobs (rows, max_seq_len, V+1) f32: the log-probability row every word was selected from, after temperature and constraint,
     zero beyond the hypothesis's length); with return_scores the list scores (rows,) come last (f32 running sums on the plain route, f64
@@ -918,13 +989,18 @@ def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=
     >= 1), decoding_constraint, length_penalty ('' | 'avg_<x>' | 'wu_<alpha>'), sample_n (1: the best finished hypothesis of each study;
     beam_size: all `beam_size` entries of its finished list, next to each other in list order).  With every option at its default and no
     log-probabilities the search issues exactly the launches it issued before the options existed.
+    return_attention: the result gains `attention` f32 (rows, max_seq_len, n_layers, S) after seq (and seq_logprobs), before the scores: for
+    every word the head-mean cross-attention weights over the S encoder tokens, one map per decoder layer (the reference's
+    decoder.layers[i].src_attn.attn, encoder_decoder.py:189,200, averaged over the heads), rows in the order of seq, zeros beyond a
+    hypothesis's length.  The maps come out of the cross-attention launch of the token step (evk_decode_attention_maps): the step keeps its
+    launch count.  Needs the session (head size 64, S <= 256, max_seq_len <= 256, EVK_DECODE_SESSION on): NotImplementedError otherwise.
     step_hook(t, logp, beam_sum): test instrument, called on the launching stream right before the bookkeeping of position t consumes
     `logp` (f32, one row of >= V+1 log-probabilities per live hypothesis; may be edited in place) with the running sums (B, beam).
     slot: which of the decoder's persistent sessions to use (searches that are in flight at the same time need different slots);
     as_iterator: return a generator that yields after every issued token step and returns the result (see _BeamSession.run_iter);
     burst: with as_iterator, token steps per native call (see _BeamSession._run_iter)."""
     beam, max_len = int(args.get('beam_size', 3)), int(args['max_seq_len'])
-    opts = beam_options(args, beam, return_logprobs)
+    opts = beam_options(args, beam, return_logprobs, return_attention)
     if beam < 1 or beam > 8 or beam > dec.vocab_size + 1:
         raise ValueError('beam_size must be in [1, 8]')
     session = _session_ok(dec, args)
@@ -934,6 +1010,8 @@ def beam_search(dec, enc_states, enc_mask, args, return_scores=False, step_hook=
     dec.eval()
     try:
         enc, src_mask = dec.encode(enc_states, enc_mask)
+        if return_attention:
+            _attention_ok(dec, args, enc.shape[1])
         if not session:
             return _beam_eager(dec, enc, src_mask, beam, max_len, opts, return_scores, step_hook)
         B, S, dev = enc.shape[0], enc.shape[1], enc.device
@@ -970,7 +1048,8 @@ def parse_sample_method(sample_method):
 
 
 @torch.no_grad()
-def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=None, uniforms=None, slot=0, as_iterator=False, burst=0):
+def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=None, uniforms=None, slot=0, as_iterator=False, burst=0,
+           return_attention=False):
     """AttModel._sample (modules/att_model.py:139-224) -> (seq (R, max_seq_len) int64 padded with [PAD], seq_logprobs (R, max_seq_len, V+1)
     f32 or None), R = B * sample_n rows with the sample_n copies of a study next to each other.  Options read from `args`: sample_method
     (parse_sample_method), temperature, sample_n, decoding_constraint, block_trigrams -- the reference blocks only the first B of the R rows
@@ -978,7 +1057,10 @@ def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=Non
     continue as [PAD] with zero log-probability rows, which is what the reference's early exit returns.
     uniforms: (R, max_seq_len) f32 in [0, 1), one per row and position, for the stochastic methods (default: torch.rand on the device, from
     args['generator'] if given); step_hook(t, logp): test instrument, called on the launching stream right before the choice at position t
-    consumes `logp` (f32 (R, >= V+1), may be edited in place); slot / as_iterator / burst: as beam_search."""
+    consumes `logp` (f32 (R, >= V+1), may be edited in place); slot / as_iterator / burst: as beam_search.
+    return_attention: the result is (seq, seq_logprobs, attention), attention f32 (R, max_seq_len, n_layers, S) as beam_search returns it
+    (rows never trade places on this route: the step history transposed), zeros at the positions after a row's [EOS]; same conditions,
+    same NotImplementedError."""
     was_training = dec.training
     dec.eval()
     try:
@@ -1005,13 +1087,17 @@ def sample(dec, enc_states, enc_mask, args, return_logprobs=False, step_hook=Non
             if tuple(uniforms.shape) != (R, max_len):
                 raise ValueError('uniforms must be (%d, %d)' % (R, max_len))
             uniforms = uniforms.to(device=dev, dtype=F32)
+        if return_attention:
+            _attention_ok(dec, args, S)
         if not _session_ok(dec, args):
             if as_iterator:
                 raise NotImplementedError('stepwise sampling needs the session path')
             return _sample_eager(dec, enc, src_mask, max_len, n, opts, return_logprobs, step_hook, uniforms)
         # ('sample' in front: a beam session's key starts with an integer)
         key = ('sample', B, n, max_len, S, dev.index, src_mask is None, slot, bool(return_logprobs), tuple(sorted(opts.items())))
-        ses = _session_for(dec, key, lambda: _SampleSession(dec, B, n, max_len, S, dev, opts, return_logprobs, slot))
+        if return_attention:
+            key = key + ('attention',)
+        ses = _session_for(dec, key, lambda: _SampleSession(dec, B, n, max_len, S, dev, opts, return_logprobs, slot, bool(return_attention)))
         if as_iterator:
             return ses.run_iter(enc, src_mask, uniforms, step_hook, burst)
         return ses.run(enc, src_mask, uniforms, step_hook)
@@ -1074,3 +1160,16 @@ def _beam_eager(dec, enc, src_mask, beam, max_len, opts, return_scores, step_hoo
     if return_scores:
         return best_seq, best_p
     return best_seq
+
+
+def attention_grid(attention, grid_hw):
+    """Split attention maps over the image tokens (..., S) into (global, patches): `global` (...,) is the weight of token 0, `patches`
+    (..., gh, gw) the remaining S - 1 weights on the trunk's feature map.  The token layout is the anchor view's, as _image_tokens produces
+    it: the global (patch-mean) token first, then the patches in row-major order -- the layout FineTune.generate_with_attention returns.  (The
+    maps of beam_search / sample themselves cover what the decoder attends to: it drops the global token, so they hold the gh * gw patch
+    columns only; generate_with_attention puts an exact zero in front.)  ValueError if gh * gw != S - 1."""
+    gh, gw = int(grid_hw[0]), int(grid_hw[1])
+    S = attention.shape[-1]
+    if gh < 1 or gw < 1 or gh * gw != S - 1:
+        raise ValueError('attention_grid: a %d x %d grid does not hold the %d patch tokens of maps over %d tokens' % (gh, gw, S - 1, S))
+    return attention[..., 0], attention[..., 1:].reshape(*attention.shape[:-1], gh, gw)

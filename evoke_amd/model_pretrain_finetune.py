@@ -180,6 +180,39 @@ class FineTune(_Base):
         return [[t if len(t) > 0 else NO_FINDING for t in gen_texts], output]
 
     @torch.no_grad()
+    def generate_with_attention(self, images, patient_ids, inc_ids=None, inc_masks=None):
+        """Reports with their grounding maps -> dict: `texts` (as forward(mode='sample') returns them), `ids` (rows, max_seq_len) int64,
+        `attention` f32 (rows, max_seq_len, n_layers, S): for every word the head-mean cross-attention weights over the S = 1 + gh * gw
+        image tokens of the anchor view in _image_tokens' layout (decode.beam_search / decode.sample with return_attention), `grid`
+        (gh, gw) of the trunk's last feature map -- decode.attention_grid(attention, grid) splits a map into the global token's weight and
+        the gh x gw patch weights.  The R2Gen decoder drops the global token in front of its encoder (EncoderDecoder.encode,
+        encoder_decoder.py:386), so the search itself attends to the gh * gw patch tokens only and column 0 is an exact zero, put there so
+        that the columns line up with the tokens.  The search route, beam or sampling, is chosen as text_decoder_forward_r2gen chooses it.
+        The number of studies is that of the indication rows when given, else the number of distinct patient ids (the anchor views come
+        first, as in forward).  NotImplementedError on the distilgpt2 backend and on geometries without a decode session (see
+        decode.beam_search)."""
+        if self.decoder_kind != 'r2gen':
+            raise NotImplementedError('generate_with_attention: the distilgpt2 backend returns no attention maps (its beam kernel keeps no '
+                                      'per-hypothesis ancestry, and head sizes 128 / 256 have a kernel of their own)')
+        from .decode import beam_search, sample
+        was_training = self.training
+        self.eval()
+        try:
+            batch = inc_ids.shape[0] if inc_ids is not None else len(dict.fromkeys(np.asarray(patient_ids).tolist()))
+            x, enc_mask = self.encoder_states(images, patient_ids, batch, inc_ids, inc_masks)
+            if decode_route(self.args) == 'beam':
+                ids, attention = beam_search(self.text_decoder, x, enc_mask, self.args, return_attention=True)
+            else:
+                ids, _, attention = sample(self.text_decoder, x, enc_mask, self.args, return_attention=True)
+        finally:
+            self.train(was_training)
+        attention = torch.cat([attention.new_zeros(*attention.shape[:-1], 1), attention], -1)
+        texts = self.tokenizer.decode_batch(ids.cpu().tolist())
+        ops.check_forward_guard(ids.device, block=True)
+        grid = (-(-images.shape[-2] // 32), -(-images.shape[-1] // 32))          # ResNet-101: five stride-2 stages, each ceil(n / 2)
+        return {'texts': [t if len(t) > 0 else NO_FINDING for t in texts], 'ids': ids, 'attention': attention, 'grid': grid}
+
+    @torch.no_grad()
     def generate_pipelined(self, batches, mode='inference', depth=None):
         """forward(..., mode=mode) over a sequence of batches, as a generator of its return values, with the device kept busy across
         batches.  The decode of a batch is a chain of ~100 x ~56 small dependent kernels: latency bound, most of the GPU idles while it

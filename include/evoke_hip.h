@@ -428,6 +428,15 @@ int evk_decode_attention_indirect(const void* q, const void* k, const void* v, c
  * (encoder_decoder.py:182-214 driven by caption_model.py:beam_search) without a copy kernel.  rowmap[r][*last_pos] must be r. */
 int evk_decode_attention_qkv(const void* qkv, int64_t ldq, void* k_cache, void* v_cache, const int32_t* rowmap, const int64_t* last_pos, void* out,
                              int32_t R, int32_t S, int32_t heads, int32_t head_dim, float scale, evk_stream_t stream);
+/* evk_decode_attention that also emits the attention weights the reference keeps on the module (MultiHeadedAttention.attn,
+ * modules/encoder_decoder.py:189,200), averaged over the heads: row r of the map, S f32 values (1/heads) * sum_h softmax_s(scale q[r,h] .
+ * K[r/kv_div, s, h]) summed in the order h = 0 .. heads-1, goes to maps + (slab_pos ? *slab_pos : 0) * slab_stride + r * maps_ld
+ * (slab_pos: device int64 scalar, the position counter of a captured decode step, or NULL).  Masked keys give exactly 0, a row whose
+ * keys are all masked a row of zeros.  Same launch, same `out` bits as evk_decode_attention; no atomics: every launch gives the same
+ * bits.  dh must be 64, 1 <= S <= 256, maps_ld >= S, R % kv_div == 0. */
+int evk_decode_attention_maps(const void* q, const void* k, const void* v, const unsigned char* mask, void* out, float* maps, int64_t maps_ld,
+                              const int64_t* slab_pos, int64_t slab_stride, int32_t R, int32_t S, int32_t heads, int32_t dh, int32_t kv_div,
+                              float scale, evk_stream_t stream);
 /* The single-query attention for head_dim 128 and 256 (decode_attn_wide.hip; the 2048-wide, 8-head decoder of the EVOKE YAML files), one
  * entry point for what the three above take at head_dim 64: q bf16 [R][ldq] read in place (ldq 0 = heads * head_dim, else a multiple of
  * 8, e.g. a fused q | k | v row), k / v bf16 [R/kv_div][S][heads * head_dim], mask uint8 [R/kv_div][S] or NULL, rowmap int32 [R][S] or
