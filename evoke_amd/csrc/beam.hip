@@ -10,7 +10,7 @@
 //      winners' order (a sample's hypotheses only permute among themselves), the new token goes to position *pos;
 //   3. finished-beam tracking and the -1000 penalty, the next step's input tokens.
 #include <stdlib.h>
-#include "common.h"
+#include "decode_step.h"
 
 namespace {
 
@@ -43,43 +43,67 @@ struct BeamOpts {
 template <bool OPTS> struct BeamArgs : BeamP {};
 template <> struct BeamArgs<true> : BeamP { BeamOpts o; };
 
-// the finished hypotheses of this step enter the study's list (thread 0 ranks, then every thread moves its columns of the list's rows:
-// entries only move DOWN, so walking the slots from the bottom up lets a thread read a column before it overwrites it -- no staging)
-__device__ __forceinline__ void finished_list_insert(const BeamP& p, const BeamOpts& o, int b, int tid, long pos, const float* win_v,
-                                                     const int* win_i, const long long* l_seq, const int* l_anc) {
-  __shared__ double f_sc[KMAX]; __shared__ int f_ln[KMAX]; __shared__ int f_src[KMAX];
-  const int n = p.beam;
+// ---- the tail of both step kernels: finished beams (best p so far; the earlier / lower beam index wins ties), the -1000 penalty, next
+// tokens; with OPTS the finished hypotheses of this step enter the study's sorted list; the row table's next column, the position advance
+template <bool OPTS>
+__device__ __forceinline__ void beam_finish(const BeamArgs<OPTS>& p, int b, int tid, long pos, const float* win_v, const int* win_i,
+                                            const long long* l_seq, const int* l_anc) {
+  __shared__ int s_best;
+  const int beam = p.beam, V1 = p.V1;
   if (tid == 0) {
-    for (int k = 0; k < n; ++k) { f_sc[k] = o.fin_score[b * n + k]; f_ln[k] = o.fin_len[b * n + k]; f_src[k] = k; }
-    const double div = (o.len_div && pos >= 0 && pos < p.max_len) ? o.len_div[pos] : 1.0;
-    for (int j = 0; j < n; ++j) {
-      if (!(p.force_end || win_i[j] % p.V1 == p.eos)) continue;
-      const double s = o.len_div ? (double)win_v[j] / div : (double)win_v[j];
-      int k = 0;
-      while (k < n && f_ln[k] != 0 && !(s > f_sc[k])) ++k;
-      if (k >= n) continue;
-      for (int q = n - 1; q > k; --q) { f_sc[q] = f_sc[q - 1]; f_ln[q] = f_ln[q - 1]; f_src[q] = f_src[q - 1]; }
-      f_sc[k] = s; f_ln[k] = (int)pos + 1; f_src[k] = n + j;
+    float pv = -INFINITY; int pi = -1;
+    for (int j = 0; j < beam; ++j) {
+      const int word = win_i[j] % V1;
+      const bool end = p.force_end || word == p.eos;
+      if (end && win_v[j] > pv) { pv = win_v[j]; pi = j; }
+      p.beam_sum[b * beam + j] = win_v[j] - (end ? 1000.f : 0.f);
+      p.words[b * beam + j] = word;
     }
-    for (int k = 0; k < n; ++k) { o.fin_score[b * n + k] = f_sc[k]; o.fin_len[b * n + k] = f_ln[k]; }
+    int take = -1;
+    if (pi >= 0 && pv > p.best_p[b]) { p.best_p[b] = pv; take = pi; }
+    s_best = take;
   }
   __syncthreads();
-  for (int c = tid; c < p.max_len; c += 256)
-    for (int d = n - 1; d >= 0; --d) {
-      const int s = f_src[d];
-      if (s == d) continue;
-      long long w; int a = 0;
-      if (s < n) {
-        w = o.fin_seq[(long)(b * n + s) * p.max_len + c];
-        if (o.fin_anc) a = o.fin_anc[(long)(b * n + s) * p.max_len + c];
-      } else {
-        const int sb = win_i[s - n] / p.V1;
-        w = c < pos ? l_seq[sb * p.max_len + c] : c == pos ? (long long)(win_i[s - n] % p.V1) : (long long)o.pad;
-        a = c < pos ? ((l_anc && c < p.anc_cols) ? l_anc[sb * p.anc_cols + c] : b * n) : c == pos ? b * n + sb : 0;
-      }
-      o.fin_seq[(long)(b * n + d) * p.max_len + c] = w;
-      if (o.fin_anc) o.fin_anc[(long)(b * n + d) * p.max_len + c] = a;
+  if (s_best >= 0) {
+    const int j = s_best, src = win_i[j] / V1;
+    for (int c = tid; c < p.max_len; c += 256)
+      p.best_seq[(long)b * p.max_len + c] = c == pos ? (long long)(win_i[j] % V1) : l_seq[src * p.max_len + c];
+  }
+  if constexpr (OPTS) {
+    // thread 0 ranks the finished hypotheses of this step into the study's list, then every thread moves its columns of the list's rows
+    __shared__ double f_sc[KMAX]; __shared__ int f_ln[KMAX]; __shared__ int f_src[KMAX];
+    const BeamOpts& o = p.o;
+    if (tid == 0) {
+      for (int k = 0; k < beam; ++k) { f_sc[k] = o.fin_score[b * beam + k]; f_ln[k] = o.fin_len[b * beam + k]; f_src[k] = k; }
+      const double div = (o.len_div && pos >= 0 && pos < p.max_len) ? o.len_div[pos] : 1.0;
+      for (int j = 0; j < beam; ++j)
+        if (p.force_end || win_i[j] % V1 == p.eos)
+          list_insert(f_sc, f_ln, f_src, beam, o.len_div ? (double)win_v[j] / div : (double)win_v[j], (int)pos + 1, j);
+      for (int k = 0; k < beam; ++k) { o.fin_score[b * beam + k] = f_sc[k]; o.fin_len[b * beam + k] = f_ln[k]; }
     }
+    __syncthreads();
+    // a fresh entry's row: the words of its source beam, the new word, [PAD]; per position the row that scored it
+    list_move_rows<256>(o.fin_seq + (long)b * beam * p.max_len, f_src, beam, p.max_len, [&](int j, int c) {
+      return c < pos ? l_seq[(win_i[j] / V1) * p.max_len + c] : c == pos ? (long long)(win_i[j] % V1) : (long long)o.pad;
+    });
+    if (o.fin_anc)
+      list_move_rows<256>(o.fin_anc + (long)b * beam * p.max_len, f_src, beam, p.max_len, [&](int j, int c) {
+        const int sb = win_i[j] / V1;
+        return c < pos ? ((l_anc && c < p.anc_cols) ? l_anc[sb * p.anc_cols + c] : b * beam) : c == pos ? b * beam + sb : 0;
+      });
+  }
+  if (p.pos_out) {
+    // the next decoder step writes its keys / values at position pos + 1 of every hypothesis's OWN cache row: seed that column of the row
+    // table here (it replaces an index_copy launch), then let the last workgroup advance the position (it replaces an add launch)
+    if (p.anc && pos + 1 < p.anc_cols && tid < beam) p.anc[(long)(b * beam + tid) * p.anc_cols + pos + 1] = b * beam + tid;
+    advance_position(p.pos_out, p.ticket, pos);
+  }
+}
+// the sequences and the row table of the sample in the winners' order, the new token at position pos
+__device__ __forceinline__ void beam_rewrite(const BeamP& p, int b, long pos, const int* win_i, const long long* l_seq, const int* l_anc) {
+  const auto src_of = [&](int j) { return win_i[j] / p.V1; };
+  rewrite_rows<256>(p.beam_seq + (long)b * p.beam * p.max_len, l_seq, p.beam, p.max_len, pos, src_of, [&](int j) { return win_i[j] % p.V1; });
+  if (p.anc) rewrite_rows<256>(p.anc + (long)b * p.beam * p.anc_cols, l_anc, p.beam, p.anc_cols, -1, src_of, [](int) { return 0; });
 }
 
 template <bool OPTS>
@@ -87,71 +111,29 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs<OPTS> p) 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float s_val[4]; __shared__ int s_idx[4];
   __shared__ float win_v[KMAX]; __shared__ int win_i[KMAX];
-  __shared__ int s_best;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int beam = p.beam;
   const long pos = p.pos[0];
-  // ---- 1. top-`beam` candidates
-  float bv[KMAX]; int bi[KMAX];
-#pragma unroll
-  for (int j = 0; j < KMAX; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-  // a thread's share of one source beam is requested in one batch (UNR loads in flight), then inserted: the step is latency bound, and
-  // one dependent L2 round trip per candidate (23 per thread at beam 4, V = 1444) was most of this kernel's time.  Which thread sees
-  // which candidate does not matter: the order (score, then lowest flat index) is total.
-  constexpr int UNR = 8;
+  // ---- 1. top-`beam` candidates: every thread keeps the best of its share, `beam` block rounds pick the winners.  With no comparable
+  // candidate left (every log-probability of the sample NaN) slot r keeps ITS OWN hypothesis and emits token 0, as in the fast kernel
+  CandList<KMAX> best;
+  best.clear();
   for (int src = 0; src < beam; ++src) {
     const float base = p.beam_sum[b * beam + src];
-    const float* row = p.logp + (long)(b * beam + src) * p.ld;
     int prev = -1; float* hrow = nullptr;
     if constexpr (OPTS) {
       if (p.o.constraint && pos > 0 && pos < p.max_len) prev = (int)p.beam_seq[((long)b * beam + src) * p.max_len + pos - 1];
       if (p.o.hist && pos >= 0 && pos < p.max_len) hrow = p.o.hist + ((long)pos * p.o.R + b * beam + src) * p.V1;
     }
-    for (int w0 = tid; w0 < p.V1; w0 += 256 * UNR) {
-      float lv[UNR];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) { const int w = w0 + 256 * u; lv[u] = w < p.V1 ? row[w] : 0.f; }
+    walk_row<256>(p.logp + (long)(b * beam + src) * p.ld, p.V1, [&](int w, float lv) {
       if constexpr (OPTS) {
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-          const int w = w0 + 256 * u;
-          if (w == prev) lv[u] = -INFINITY;
-          if (hrow && w < p.V1) hrow[w] = lv[u];
-        }
+        if (w == prev) lv = -INFINITY;
+        if (hrow) hrow[w] = lv;
       }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int w = w0 + 256 * u;
-        if (w >= p.V1) continue;
-        float v = base + lv[u];
-        int id = src * p.V1 + w;
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j)
-          if (j < beam && (v > bv[j] || (v == bv[j] && id < bi[j]))) { const float tv = bv[j]; const int ti = bi[j]; bv[j] = v; bi[j] = id; v = tv; id = ti; }
-      }
-    }
+      best.insert(base + lv, src * p.V1 + w, beam);
+    });
   }
-  for (int r = 0; r < beam; ++r) {
-    float best = bv[0]; int bid = bi[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bid, o, 64);
-      if (ov > best || (ov == best && oi < bid)) { best = ov; bid = oi; }
-    }
-    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bid; }
-    __syncthreads();
-    if (tid == 0) {
-      float fv = s_val[0]; int fi = s_idx[0];
-      for (int w = 1; w < 4; ++w) if (s_val[w] > fv || (s_val[w] == fv && s_idx[w] < fi)) { fv = s_val[w]; fi = s_idx[w]; }
-      win_v[r] = fv; win_i[r] = fi;
-    }
-    __syncthreads();
-    if (bi[0] == win_i[r]) {            // the owner pops its head
-#pragma unroll
-      for (int j = 0; j + 1 < KMAX; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-      bv[KMAX - 1] = -INFINITY; bi[KMAX - 1] = 0x7fffffff;
-    }
-  }
+  pick_rounds<256>(best, beam, p.V1, s_val, s_idx, win_v, win_i);
   // ---- 2. stage the sample's rows, rewrite them in the winners' order
   long long* seq = p.beam_seq + (long)b * beam * p.max_len;
   long long* l_seq = reinterpret_cast<long long*>(smem);                               // [beam][max_len]
@@ -165,16 +147,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs<OPTS> p) 
     for (int i = tid; i < beam * mw; i += 256) l_mem[i] = gm[i];
   }
   __syncthreads();
-  for (int i = tid; i < beam * p.max_len; i += 256) {
-    const int j = i / p.max_len, c = i - j * p.max_len;
-    const int src = win_i[j] / p.V1;
-    seq[i] = c == pos ? (long long)(win_i[j] - src * p.V1) : l_seq[src * p.max_len + c];
-  }
-  if (p.anc)
-    for (int i = tid; i < beam * p.anc_cols; i += 256) {
-      const int j = i / p.anc_cols, c = i - j * p.anc_cols;
-      p.anc[(long)b * beam * p.anc_cols + i] = l_anc[(win_i[j] / p.V1) * p.anc_cols + c];
-    }
+  beam_rewrite(p, b, pos, win_i, l_seq, l_anc);
   if (p.mem) {
     uint32_t* gm = reinterpret_cast<uint32_t*>(p.mem + (long)b * beam * p.mem_row);
     for (int i = tid; i < beam * mw; i += 256) {
@@ -192,37 +165,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs<OPTS> p) 
       gm[i] = l_mem[(win_i[j] / p.V1) * mw + c];
     }
   }
-  // ---- 3. finished beams (best p so far; the earlier / lower beam index wins ties), the -1000 penalty, next tokens
-  if (tid == 0) {
-    float pv = -INFINITY; int pi = -1;
-    for (int j = 0; j < beam; ++j) {
-      const int word = win_i[j] % p.V1;
-      const bool end = p.force_end || word == p.eos;
-      if (end && win_v[j] > pv) { pv = win_v[j]; pi = j; }
-      p.beam_sum[b * beam + j] = win_v[j] - (end ? 1000.f : 0.f);
-      p.words[b * beam + j] = word;
-    }
-    int take = -1;
-    if (pi >= 0 && pv > p.best_p[b]) { p.best_p[b] = pv; take = pi; }
-    s_best = take;
-  }
-  __syncthreads();
-  if (s_best >= 0) {
-    const int j = s_best, src = win_i[j] / p.V1;
-    for (int c = tid; c < p.max_len; c += 256)
-      p.best_seq[(long)b * p.max_len + c] = c == pos ? (long long)(win_i[j] % p.V1) : l_seq[src * p.max_len + c];
-  }
-  if constexpr (OPTS) finished_list_insert(p, p.o, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
-  if (p.pos_out) {
-    // the next decoder step writes its keys / values at position pos + 1 of every hypothesis's OWN cache row: seed that column of the row
-    // table here (it replaces an index_copy launch), then let the last workgroup advance the position (it replaces an add launch)
-    if (p.anc && pos + 1 < p.anc_cols && tid < beam) p.anc[(long)(b * beam + tid) * p.anc_cols + pos + 1] = b * beam + tid;
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
-    }
-  }
+  // ---- 3. finished beams, the -1000 penalty, next tokens, the position advance
+  beam_finish<OPTS>(p, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
 }
 
 // The same step with ONE memory round trip in front of the selection: the sample's state rows (sequences, cache row table, memory) and
@@ -240,7 +184,7 @@ template <int CTRL>
 __device__ __forceinline__ void dpp_argmax_step(float& v, int& i) {
   const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
   const int oi = __builtin_amdgcn_update_dpp(0, i, CTRL, 0xF, 0xF, true);
-  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  if (better(ov, oi, v, i)) { v = ov; i = oi; }
 }
 __device__ __forceinline__ void wave_argmax(float& v, int& i) {
   dpp_argmax_step<0xB1>(v, i);       // quad_perm [1,0,3,2]
@@ -253,7 +197,7 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
   for (int r = 1; r < 4; ++r) {
     const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16 * r));
     const int oi = __builtin_amdgcn_readlane(i, 16 * r);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
   v = bv; i = bi;
 }
@@ -263,7 +207,6 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamArgs<OPTS
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float c_val[KMAX * KMAX]; __shared__ int c_idx[KMAX * KMAX];
   __shared__ float win_v[KMAX]; __shared__ int win_i[KMAX];
-  __shared__ int s_best;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int beam = p.beam, V1 = p.V1;
   const long pos = p.pos[0];
@@ -327,7 +270,7 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamArgs<OPTS
 #pragma unroll
     for (int i = 0; i < CMAX; ++i) x[u][i] += base[u];            // -inf stays -inf
     for (int r = 0; r < beam; ++r) {
-      float bv = -INFINITY; int bi = 0x7fffffff;
+      float bv = -INFINITY; int bi = NO_CAND;
 #pragma unroll
       for (int i = 0; i < CMAX; ++i) if (x[u][i] > bv) { bv = x[u][i]; bi = src * V1 + lane + 64 * i; }      // ascending index: ties keep the lowest
       wave_argmax(bv, bi);
@@ -343,29 +286,20 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamArgs<OPTS
   // ---- 2. merge the beam x beam survivors (wave 0)
   if (wave == 0) {
     float v = lane < beam * beam ? c_val[lane] : -INFINITY;
-    int id = lane < beam * beam ? c_idx[lane] : 0x7fffffff;
+    int id = lane < beam * beam ? c_idx[lane] : NO_CAND;
     for (int r = 0; r < beam; ++r) {
       float bv = v; int bi = id;
       wave_argmax(bv, bi);
       // No comparable candidate left (every log-probability of the sample NaN or -inf: the forward guard only scans the trunk output): the
       // sentinel index would address LDS rows beyond the sample's beams below -- slot r then keeps ITS OWN hypothesis and emits token 0 ([PAD]),
       // a defined state instead of garbage.
-      if (lane == 0) { win_v[r] = bv; win_i[r] = bi == 0x7fffffff ? r * V1 : bi; }
-      if (id == bi) { v = -INFINITY; id = 0x7fffffff; }
+      if (lane == 0) { win_v[r] = bv; win_i[r] = bi == NO_CAND ? r * V1 : bi; }
+      if (id == bi) { v = -INFINITY; id = NO_CAND; }
     }
   }
   __syncthreads();
   // ---- 3. rewrite the sample's rows in the winners' order (a sample's hypotheses only permute among themselves)
-  for (int i = tid; i < beam * p.max_len; i += 256) {
-    const int j = i / p.max_len, c = i - j * p.max_len;
-    const int src = win_i[j] / V1;
-    seq[i] = c == pos ? (long long)(win_i[j] - src * V1) : l_seq[src * p.max_len + c];
-  }
-  if (p.anc)
-    for (int i = tid; i < beam * p.anc_cols; i += 256) {
-      const int j = i / p.anc_cols, c = i - j * p.anc_cols;
-      p.anc[(long)b * beam * p.anc_cols + i] = l_anc[(win_i[j] / V1) * p.anc_cols + c];
-    }
+  beam_rewrite(p, b, pos, win_i, l_seq, l_anc);
   auto permute_rows = [&](void* g, const uint32_t* l) {          // row j <- staged row of its source beam; rows that stay are not rewritten
     if ((mw & 3) == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(l)) & 15) == 0) {
       const int w4 = mw >> 2;
@@ -384,35 +318,8 @@ __global__ __launch_bounds__(256) void beam_step_fast_kernel(const BeamArgs<OPTS
   };
   if (p.mem) permute_rows(p.mem + (long)b * beam * p.mem_row, l_mem);
   if (p.mem2) permute_rows(p.mem2 + (long)b * beam * p.mem_row, l_mem2);
-  // ---- 4. finished beams (best p so far; the earlier / lower beam index wins ties), the -1000 penalty, next tokens
-  if (tid == 0) {
-    float pv = -INFINITY; int pi = -1;
-    for (int j = 0; j < beam; ++j) {
-      const int word = win_i[j] % V1;
-      const bool end = p.force_end || word == p.eos;
-      if (end && win_v[j] > pv) { pv = win_v[j]; pi = j; }
-      p.beam_sum[b * beam + j] = win_v[j] - (end ? 1000.f : 0.f);
-      p.words[b * beam + j] = word;
-    }
-    int take = -1;
-    if (pi >= 0 && pv > p.best_p[b]) { p.best_p[b] = pv; take = pi; }
-    s_best = take;
-  }
-  __syncthreads();
-  if (s_best >= 0) {
-    const int j = s_best, src = win_i[j] / V1;
-    for (int c = tid; c < p.max_len; c += 256)
-      p.best_seq[(long)b * p.max_len + c] = c == pos ? (long long)(win_i[j] % V1) : l_seq[src * p.max_len + c];
-  }
-  if constexpr (OPTS) finished_list_insert(p, p.o, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
-  if (p.pos_out) {
-    if (p.anc && pos + 1 < p.anc_cols && tid < beam) p.anc[(long)(b * beam + tid) * p.anc_cols + pos + 1] = b * beam + tid;
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
-    }
-  }
+  // ---- 4. finished beams, the -1000 penalty, next tokens, the position advance
+  beam_finish<OPTS>(p, b, tid, pos, win_v, win_i, l_seq, p.anc ? l_anc : nullptr);
 }
 
 // out[b * take + k][t][:] = hist[t][fin_anc[b][k][t]][:] for t < fin_len[b][k], zeros beyond: the seqLogprobs rows of the returned

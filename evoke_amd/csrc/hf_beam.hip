@@ -17,11 +17,11 @@
 // place), and the scorer's length_penalty (a host-computed table of divisors cur_len ** length_penalty) and early_stopping.
 #include <stdlib.h>
 #include "common.h"
+#include "decode_step.h"
 
 namespace {
 
 constexpr int NBMAX = 8;
-constexpr int NGRAM_MAX = 8;
 
 struct HfBeamP {
   const float* logp; int ld;           // [B*nb][ld] f32 log-probs of the step, V valid columns
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const P p) {
   __shared__ float nx_sc[NBMAX]; __shared__ int nx_tok[NBMAX]; __shared__ int nx_src[NBMAX];
   __shared__ double f_sc[NBMAX]; __shared__ int f_ln[NBMAX]; __shared__ int f_src[NBMAX];
   __shared__ int s_list;               // the list's rows move in this launch
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int nb = p.nb, V = p.V, k2 = 2 * nb;
   const long pos = p.pos[0];
   const bool was_done = p.done[b] != 0;                       // (block-uniform)
@@ -69,86 +69,25 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const P p) {
       const int ml = p.max_len, cur = min((int)pos + 1, ml);      // ids so far, [BOS] included
       float* rows = const_cast<float*>(p.logp) + (long)b * nb * p.ld;
       if (p.rep_penalty != 1.f) {
-        // every distinct id of a history once: the thread that holds its first occurrence rewrites the entry
-        for (int j = 0; j < nb; ++j) {
-          const long long* h = l_seq + j * ml;
-          for (int c = tid; c < cur; c += 256) {
-            const long long w = h[c];
-            bool first = w >= 0 && w < V;
-            for (int q = 0; q < c && first; ++q) first = h[q] != w;
-            if (first) { float* x = rows + (long)j * p.ld + w; const float v = *x; *x = v < 0.f ? v * p.rep_penalty : v / p.rep_penalty; }
-          }
-        }
+        for (int j = 0; j < nb; ++j) hf_repetition_penalty<256>(rows + (long)j * p.ld, l_seq + j * ml, cur, V, p.rep_penalty);
         __syncthreads();                                       // a ban below must not be overwritten by a penalty's read-modify-write
       }
       const int g = p.ctl & 15;
-      if (g > 0 && cur >= g) {
-        // every earlier window of g ids that starts like the last g - 1 ids bans its own last id (several windows: the same store)
-        const int nwin = cur - g + 1, tail = cur - (g - 1);
-        for (int j = 0; j < nb; ++j) {
-          const long long* h = l_seq + j * ml;
-          for (int c = tid; c < nwin; c += 256) {
-            bool same = true;
-            for (int q = 0; q < g - 1 && same; ++q) same = h[c + q] == h[tail + q];
-            const long long w = h[c + g - 1];
-            if (same && w >= 0 && w < V) rows[(long)j * p.ld + w] = -INFINITY;
-          }
-        }
-      }
-      if (cur < (p.ctl >> 8) && tid < nb) rows[(long)tid * p.ld + p.eos] = -INFINITY;
+      if (g > 0 && cur >= g)
+        for (int j = 0; j < nb; ++j) hf_ban_ngrams<256>(rows + (long)j * p.ld, l_seq + j * ml, cur, V, g);
+      if (cur < (p.ctl >> 8) && tid < nb) hf_min_length(rows + (long)tid * p.ld, p.eos);
       __syncthreads();                                         // the rows are re-read by this workgroup only
     }
   }
   if (!was_done) {
-    // ---- 1. the 2 * nb best candidates, descending
-    float bv[K2]; int bi[K2];
-#pragma unroll
-    for (int j = 0; j < K2; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
-    constexpr int UNR = 8;             // a thread's share of one source beam is requested in one batch, then inserted (see beam.hip)
+    // ---- 1. the 2 * nb best candidates, descending (no comparable candidate left: rank r takes source beam 0, token r < V, at -inf)
+    CandList<K2> best;
+    best.clear();
     for (int src = 0; src < nb; ++src) {
       const float base = p.scores[b * nb + src];
-      const float* row = p.logp + (long)(b * nb + src) * p.ld;
-      for (int w0 = tid; w0 < V; w0 += 256 * UNR) {
-        float lv[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) { const int w = w0 + 256 * u; lv[u] = w < V ? row[w] : 0.f; }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-          const int w = w0 + 256 * u;
-          if (w >= V) continue;
-          float v = base + lv[u];
-          int id = src * V + w;
-          if (!(v > bv[K2 - 1] || (v == bv[K2 - 1] && id < bi[K2 - 1])) && k2 == K2) continue;     // (cannot enter a full-depth list)
-#pragma unroll
-          for (int j = 0; j < K2; ++j)
-            if (j < k2 && (v > bv[j] || (v == bv[j] && id < bi[j]))) { const float tv = bv[j]; const int ti = bi[j]; bv[j] = v; bi[j] = id; v = tv; id = ti; }
-        }
-      }
+      walk_row<256>(p.logp + (long)(b * nb + src) * p.ld, V, [&](int w, float lv) { best.insert(base + lv, src * V + w, k2); });
     }
-    for (int r = 0; r < k2; ++r) {
-      float best = bv[0]; int bid = bi[0];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bid, o, 64);
-        if (ov > best || (ov == best && oi < bid)) { best = ov; bid = oi; }
-      }
-      if (lane == 0) { s_val[wave] = best; s_idx[wave] = bid; }
-      __syncthreads();
-      if (tid == 0) {
-        float fv = s_val[0]; int fi = s_idx[0];
-        for (int w = 1; w < 4; ++w) if (s_val[w] > fv || (s_val[w] == fv && s_idx[w] < fi)) { fv = s_val[w]; fi = s_idx[w]; }
-        // no comparable candidate left (every remaining log-probability NaN): rank r takes flat index r (source beam 0, token r < V) at
-        // -inf, a defined in-range state instead of a sentinel that would address rows beyond the study's beams below
-        if (fi == 0x7fffffff) { fv = -INFINITY; fi = r; }
-        win_v[r] = fv; win_i[r] = fi;
-      }
-      __syncthreads();
-      if (bi[0] == win_i[r]) {          // the owner pops its head
-#pragma unroll
-        for (int j = 0; j + 1 < K2; ++j) { bv[j] = bv[j + 1]; bi[j] = bi[j + 1]; }
-        bv[K2 - 1] = -INFINITY; bi[K2 - 1] = 0x7fffffff;
-      }
-    }
+    pick_rounds<256>(best, k2, 1, s_val, s_idx, win_v, win_i);
   }
   // ---- 2. the rank walk (thread 0): hypothesis list, next beams, done flag
   if (tid == 0) {
@@ -160,16 +99,8 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const P p) {
       if constexpr (P::kOpts) { if (p.len_div) cur_len = p.len_div[pos + 1]; }
       int nx_rank[NBMAX];
       for (int k = 0; k < nb; ++k) { f_sc[k] = p.hyp_score[b * nb + k]; f_ln[k] = p.hyp_len[b * nb + k]; f_src[k] = k; }
-      // an entry enters below every entry that is at least as good (Python's stable sort of the appended list), the list is cut to nb;
-      // f_src remembers where a slot's row comes from: an old slot (< nb) or the candidate of rank f_src - nb
-      auto insert = [&](double s, int rank) {
-        int k = 0;
-        while (k < nb && f_ln[k] != 0 && !(s > f_sc[k])) ++k;
-        if (k >= nb) return;
-        for (int q = nb - 1; q > k; --q) { f_sc[q] = f_sc[q - 1]; f_ln[q] = f_ln[q - 1]; f_src[q] = f_src[q - 1]; }
-        f_sc[k] = s; f_ln[k] = (int)pos + 2; f_src[k] = nb + rank;
-        moved = 1;
-      };
+      // the study's list in LDS; a fresh entry is named by its candidate's rank, its length is pos + 2 columns
+      auto insert = [&](double s, int rank) { if (list_insert(f_sc, f_ln, f_src, nb, s, (int)pos + 2, rank)) moved = 1; };
       int k = 0;
       for (int rank = 0; rank < k2 && k < nb; ++rank) {
         const int src = win_i[rank] / V, tok = win_i[rank] - src * V;
@@ -191,40 +122,19 @@ __global__ __launch_bounds__(256) void hf_beam_step_kernel(const P p) {
     s_list = moved;
   }
   __syncthreads();
-  // ---- 3. the list's rows: entries only move DOWN, so walking the slots from the bottom up lets a thread read a column before it
-  // overwrites it (as finished_list_insert of beam.hip)
+  // ---- 3. the list's rows follow: a fresh entry is its source beam's row, the new token in column pos + 1, [PAD] beyond
   if (s_list)
-    for (int c = tid; c < p.max_len; c += 256)
-      for (int d = nb - 1; d >= 0; --d) {
-        const int s = f_src[d];
-        if (s == d) continue;
-        long long w;
-        if (s < nb) w = p.hyp_seq[(long)(b * nb + s) * p.max_len + c];
-        else {
-          const int src = win_i[s - nb] / V;
-          w = c <= pos ? l_seq[src * p.max_len + c] : c == pos + 1 ? (long long)(win_i[s - nb] - src * V) : (long long)p.pad;
-        }
-        p.hyp_seq[(long)(b * nb + d) * p.max_len + c] = w;
-      }
-  // ---- 4. the study's rows in the winners' order, the new token in column pos + 1
-  for (int i = tid; i < nb * p.max_len; i += 256) {
-    const int j = i / p.max_len, c = i - j * p.max_len;
-    seq[i] = c == pos + 1 ? (long long)nx_tok[j] : l_seq[nx_src[j] * p.max_len + c];
-  }
-  if (p.anc)
-    for (int i = tid; i < nb * p.anc_cols; i += 256) {
-      const int j = i / p.anc_cols, c = i - j * p.anc_cols;
-      // the next decoder step writes its keys / values at position pos + 1 of every hypothesis's OWN cache row
-      p.anc[(long)b * nb * p.anc_cols + i] = c == pos + 1 ? b * nb + j : l_anc[nx_src[j] * p.anc_cols + c];
-    }
+    list_move_rows<256>(p.hyp_seq + (long)b * nb * p.max_len, f_src, nb, p.max_len, [&](int rank, int c) {
+      const int src = win_i[rank] / V;
+      return c <= pos ? l_seq[src * p.max_len + c] : c == pos + 1 ? (long long)(win_i[rank] - src * V) : (long long)p.pad;
+    });
+  // ---- 4. the study's rows in the winners' order, the new token in column pos + 1; the next decoder step writes its keys / values at
+  // position pos + 1 of every hypothesis's OWN cache row
+  const auto src_of = [&](int j) { return nx_src[j]; };
+  rewrite_rows<256>(seq, l_seq, nb, p.max_len, pos + 1, src_of, [&](int j) { return nx_tok[j]; });
+  if (p.anc) rewrite_rows<256>(p.anc + (long)b * nb * p.anc_cols, l_anc, nb, p.anc_cols, pos + 1, src_of, [&](int j) { return b * nb + j; });
   if (tid < nb) { p.scores[b * nb + tid] = nx_sc[tid]; p.words[b * nb + tid] = nx_tok[tid]; }
-  if (p.pos_out) {
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
-    }
-  }
+  if (p.pos_out) advance_position(p.pos_out, p.ticket, pos);
 }
 
 }  // namespace

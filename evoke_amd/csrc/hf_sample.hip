@@ -12,15 +12,13 @@
 // caller supplies (no generator state in the kernel: a replayed graph reads a refilled buffer).
 #include <stdlib.h>
 #include "common.h"
+#include "decode_step.h"
 
 namespace {
 
 constexpr int NT = 256;            // threads per workgroup (4 waves)
-constexpr int UNR = 8;             // row elements a thread requests before it uses the first one
 constexpr int V_MAX = 12288;       // one f32 row of V in LDS (48 KB)
 constexpr int LEN_MAX = 256;       // the row's history in LDS (1 KB)
-constexpr int NGRAM_MAX = 8;
-constexpr int NONE = 0x7fffffff;
 
 struct HfSampleP {
   const float* logits; int ld;        // [R][ld] f32 raw logits of the step, V valid columns
@@ -37,41 +35,11 @@ struct HfSampleP {
   long long* pos_out; int* ticket;    // advance: the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
 };
 
-// block-wide reductions: per-wave shuffle, then one LDS round; the result is returned to every thread
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* s_val, int* s_idx) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  __syncthreads();                    // (the scratch words may still be read from an earlier round)
-  if (lane == 0) { s_val[wave] = v; s_idx[wave] = i; }
-  __syncthreads();
-  v = s_val[0]; i = s_idx[0];
-#pragma unroll
-  for (int w = 1; w < NT / 64; ++w) if (s_val[w] > v || (s_val[w] == v && s_idx[w] < i)) { v = s_val[w]; i = s_idx[w]; }
-}
-__device__ __forceinline__ float block_sum(float v, float* s_val) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) s_val[wave] = v;
-  __syncthreads();
-  v = s_val[0];
-#pragma unroll
-  for (int w = 1; w < NT / 64; ++w) v += s_val[w];
-  return v;
-}
-// order-preserving image of a float in the unsigned integers
-__device__ __forceinline__ uint32_t fkey(float f) { const uint32_t b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
-
 __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float s_val[NT / 64]; __shared__ int s_idx[NT / 64];
   __shared__ float s_scan[NT / 64];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x, tid = threadIdx.x;
   const int V = p.V;
   float* x = reinterpret_cast<float*>(smem);                 // [V] the row as the processors leave it
   int* l_seq = reinterpret_cast<int*>(x + V);                // [max_len] the row's history
@@ -87,51 +55,31 @@ __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
       const long long w = c < cur ? seq[c] : -1;
       l_seq[c] = (w >= 0 && w < V) ? (int)w : -1;            // (an id outside the row touches nothing below)
     }
-    for (int w0 = tid; w0 < V; w0 += NT * UNR) {
-      float lv[UNR];
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; lv[q] = w < V ? row[w] : 0.f; }
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; if (w < V) x[w] = lv[q]; }
-    }
+    walk_row<NT>(row, V, [&](int w, float v) { x[w] = v; });
     __syncthreads();
-    // ---- 1. repetition penalty: every distinct id of the history once (the first occurrence's thread applies it)
+    // ---- 1. repetition penalty, 2. no-repeat n-grams, 3. minimum length
     if (p.rep_penalty != 1.f) {
-      for (int c = tid; c < cur; c += NT) {
-        const int w = l_seq[c];
-        bool first = w >= 0;
-        for (int j = 0; j < c && first; ++j) first = l_seq[j] != w;
-        if (first) { const float v = x[w]; x[w] = v < 0.f ? v * p.rep_penalty : v / p.rep_penalty; }
-      }
+      hf_repetition_penalty<NT>(x, l_seq, cur, V, p.rep_penalty);
       __syncthreads();
     }
-    // ---- 2. no-repeat n-grams: every earlier window of g ids that starts like the last g - 1 ids bans its own last id
-    const int g = p.ngram;
-    if (g > 0 && cur >= g) {
-      const int tail = cur - (g - 1);                        // the last g - 1 ids: l_seq[tail .. cur - 1]
-      for (int i = tid; i + g <= cur; i += NT) {
-        bool same = true;
-        for (int j = 0; j < g - 1 && same; ++j) same = l_seq[i + j] == l_seq[tail + j];
-        const int w = l_seq[i + g - 1];
-        if (same && w >= 0) x[w] = -INFINITY;                // (several windows may ban the same id: the same store)
-      }
+    if (p.ngram > 0 && cur >= p.ngram) {
+      hf_ban_ngrams<NT>(x, l_seq, cur, V, p.ngram);
       __syncthreads();
     }
-    // ---- 3. minimum length
     if (cur < p.min_length) {
-      if (tid == 0) x[p.eos] = -INFINITY;
+      if (tid == 0) hf_min_length(x, p.eos);
       __syncthreads();
     }
     // ---- 4. temperature (a division, as HF's), the row's arg-max
-    float bv = -INFINITY; int bi = NONE;
+    float bv = -INFINITY; int bi = NO_CAND;
     for (int w = tid; w < V; w += NT) {
       float v = x[w];
       if (p.do_sample && p.temperature != 1.f) { v = v / p.temperature; x[w] = v; }      // (own entries only: no barrier needed)
       if (v > bv) { bv = v; bi = w; }                        // ascending index: ties keep the lowest
     }
-    block_argmax(bv, bi, s_val, s_idx);
-    const bool empty = bi == NONE || !(bv > -INFINITY) || !(bv < INFINITY);     // no entry to choose from (all -inf / NaN), or an infinite one
-    int it = bi == NONE ? p.pad : bi;
+    block_argmax<NT>(bv, bi, s_val, s_idx);
+    const bool empty = bi == NO_CAND || !(bv > -INFINITY) || !(bv < INFINITY);     // no entry to choose from (all -inf / NaN), or an infinite one
+    int it = bi == NO_CAND ? p.pad : bi;
     uint32_t thr = 0u;                                       // the smallest kept key (0: everything stays)
     if (p.do_sample && !empty) {
       // ---- 5. top-k: the key of the k-th largest value = the smallest m with fewer than k entries above it
@@ -142,7 +90,7 @@ __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
           const uint32_t mid = lo + ((hi - lo) >> 1);
           float a = 0.f;
           for (int w = tid; w < V; w += NT) a += fkey(x[w]) > mid ? 1.f : 0.f;
-          if (block_sum(a, s_val) < k) hi = mid; else lo = mid + 1;
+          if (block_sum<NT>(a, s_val) < k) hi = mid; else lo = mid + 1;
         }
         thr = hi;
       }
@@ -151,7 +99,7 @@ __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
         auto below = [&](uint32_t m) {                       // mass of the kept entries with key <= m
           float a = 0.f;
           for (int w = tid; w < V; w += NT) { const uint32_t kx = fkey(x[w]); if (kx >= thr && kx <= m) a += expf(x[w] - bv); }
-          return block_sum(a, s_val);
+          return block_sum<NT>(a, s_val);
         };
         const uint32_t top = fkey(bv);
         const float limit = (1.f - p.top_p) * below(top);
@@ -176,39 +124,9 @@ __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
       if (out) out[w] = v;
       if (!empty) part += expf(v - bv);                      // (exp(-inf) = 0)
     }
-    const float total = empty ? 1.f : block_sum(part, s_val);
-    // ---- 8. the draw: inverse CDF in vocabulary order -- a thread owns a contiguous piece, a wave scans its 64 pieces, wave totals meet in LDS
-    if (p.do_sample && !empty) {
-      const int C = (V + NT - 1) / NT, c0 = min(V, tid * C), c1 = min(V, c0 + C);
-      float own = 0.f;
-      for (int j = c0; j < c1; ++j) own += expf(x[j] - bv);
-      float inc = own;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(inc, o, 64); if (lane >= o) inc += up; }
-      __syncthreads();
-      if (lane == 63) s_scan[wave] = inc;
-      __syncthreads();
-      float base = 0.f, all = 0.f;
-#pragma unroll
-      for (int w = 0; w < NT / 64; ++w) { if (w < wave) base += s_scan[w]; all += s_scan[w]; }
-      const float target = u * all;
-      float run = base + inc - own;
-      float cv = -INFINITY; int ci = NONE;                   // the first column whose running sum exceeds the target: arg-max of (0, lowest index)
-      int last = -1;                                         // the highest kept column (target >= the rounded total: u next to 1)
-      for (int j = c0; j < c1; ++j) {
-        const float k = expf(x[j] - bv);
-        run += k;
-        if (k > 0.f) last = j;
-        if (ci == NONE && k > 0.f && run > target) { cv = 0.f; ci = j; }
-      }
-      block_argmax(cv, ci, s_val, s_idx);
-      if (ci == NONE) {
-        float lv = last < 0 ? -INFINITY : 0.f; int li = last < 0 ? NONE : -last;      // highest index = lowest negated index among equal keys
-        block_argmax(lv, li, s_val, s_idx);
-        ci = li == NONE ? it : -li;
-      }
-      it = ci;
-    }
+    const float total = empty ? 1.f : block_sum<NT>(part, s_val);
+    // ---- 8. the draw: inverse CDF over the kept entries in vocabulary order (a removed entry weighs exp(-inf) = 0)
+    if (p.do_sample && !empty) it = draw_inverse_cdf<NT>(V, u, it, [&](int j) { return expf(x[j] - bv); }, s_scan, s_val, s_idx);
     // ---- 9. finished rows emit [PAD]; a row finishes when it emits [EOS]
     if (tid == 0) {
       float lp = empty ? 0.f : (x[it] - bv) - logf(total);
@@ -219,13 +137,7 @@ __global__ __launch_bounds__(NT) void hf_sample_step_kernel(const HfSampleP p) {
       if (p.tok_logp) p.tok_logp[(long)r * p.max_len + cur] = lp;
     }
   }
-  if (p.pos_out) {
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = pos + 1; }
-    }
-  }
+  if (p.pos_out) advance_position(p.pos_out, p.ticket, pos);
 }
 
 }  // namespace

@@ -7,11 +7,11 @@
 // Rows are independent (no hypothesis re-ordering), so unlike beam.hip nothing of the decoder's state is touched.
 #include <stdlib.h>
 #include "common.h"
+#include "decode_step.h"
 
 namespace {
 
 constexpr int NT = 256;            // threads per workgroup (4 waves)
-constexpr int UNR = 8;             // row elements a thread requests before it uses the first one
 constexpr int V1_MAX = 4096;       // three f32 rows of V1 in LDS
 
 enum { M_GREEDY = 0, M_SAMPLE = 1, M_TOPK = 2, M_TOPP = 3 };
@@ -29,39 +29,11 @@ struct SampleP {
   long long* pos_out; int* ticket;    // advance: the LAST workgroup to finish writes *pos_out = pos + 1 (every workgroup has read pos by then)
 };
 
-// block-wide reductions: per-wave shuffle, then one LDS round; the result is returned to every thread
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* s_val, int* s_idx) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  __syncthreads();                    // (the scratch words may still be read from an earlier round)
-  if (lane == 0) { s_val[wave] = v; s_idx[wave] = i; }
-  __syncthreads();
-  v = s_val[0]; i = s_idx[0];
-#pragma unroll
-  for (int w = 1; w < NT / 64; ++w) if (s_val[w] > v || (s_val[w] == v && s_idx[w] < i)) { v = s_val[w]; i = s_idx[w]; }
-}
-__device__ __forceinline__ float block_sum(float v, float* s_val) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) s_val[wave] = v;
-  __syncthreads();
-  v = s_val[0];
-#pragma unroll
-  for (int w = 1; w < NT / 64; ++w) v += s_val[w];
-  return v;
-}
-
 __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float s_val[NT / 64]; __shared__ int s_idx[NT / 64];
   __shared__ float s_scan[NT / 64];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x, tid = threadIdx.x;
   const int V1 = p.V1;
   float* x = reinterpret_cast<float*>(smem);                 // [V1] the row after the constraint and the trigram penalty
   int* cnt = reinterpret_cast<int*>(x + V1);                 // [V1] trigram counts; later the row's softmax weights
@@ -77,13 +49,7 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
     const float u = p.uniforms ? p.uniforms[(long)r * p.max_len + t] : 0.f;
     const bool blocking = t >= 3 && r < p.block_rows;
     for (int c = tid; c < p.max_len; c += NT) l_seq[c] = c < t ? (int)seq[c] : -1;
-    for (int w0 = tid; w0 < V1; w0 += NT * UNR) {
-      float lv[UNR];
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; lv[q] = w < V1 ? row[w] : 0.f; }
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) { const int w = w0 + NT * q; if (w < V1) { x[w] = lv[q]; cnt[w] = 0; } }
-    }
+    walk_row<NT>(row, V1, [&](int w, float v) { x[w] = v; cnt[w] = 0; });
     __syncthreads();
     // ---- 1. decoding constraint: the previous word cannot follow itself
     if (p.constraint && t > 0 && tid == 0) { const int w = l_seq[t - 1]; if (w >= 0 && w < V1) x[w] = -INFINITY; }
@@ -97,7 +63,7 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
     }
     __syncthreads();
     // ---- 3. the penalty, the stored row (zeros for a finished row) and the row's arg-max in one pass
-    float bv = -INFINITY; int bi = 0x7fffffff;
+    float bv = -INFINITY; int bi = NO_CAND;
     float* out = p.seq_logprobs ? p.seq_logprobs + ((long)r * p.max_len + t) * V1 : nullptr;
     for (int w = tid; w < V1; w += NT) {
       float v = x[w];
@@ -105,14 +71,14 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
       if (out) out[w] = fin ? 0.f : v;
       if (v > bv) { bv = v; bi = w; }                        // ascending index: ties keep the lowest
     }
-    block_argmax(bv, bi, s_val, s_idx);
-    int it = bi == 0x7fffffff ? 0 : bi;                      // no comparable entry (the whole row NaN / -inf): a defined token, [PAD]'s column
+    block_argmax<NT>(bv, bi, s_val, s_idx);
+    int it = bi == NO_CAND ? 0 : bi;                         // no comparable entry (the whole row NaN / -inf): a defined token, [PAD]'s column
     // ---- 4. the stochastic methods: temperature, filter, inverse-CDF draw
-    if (p.method != M_GREEDY && bi != 0x7fffffff) {
+    if (p.method != M_GREEDY && bi != NO_CAND) {
       const float ymax = bv / p.temperature;
       float part = 0.f;
       for (int w = tid; w < V1; w += NT) { const float e = expf(x[w] / p.temperature - ymax); wgt[w] = e; part += e; }
-      const float total = block_sum(part, s_val);            // (its barriers also publish wgt)
+      const float total = block_sum<NT>(part, s_val);        // (its barriers also publish wgt)
       if (p.method == M_SAMPLE) {
         for (int w = tid; w < V1; w += NT) kept[w] = wgt[w];
       } else {
@@ -122,62 +88,32 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
         // value in <= 32 block reductions (a sort of the padded row would take 66 exchange stages).
         const bool by_count = p.method == M_TOPK;
         const float limit = by_count ? (float)(int)p.param : p.param * total;
-        auto key = [](float f) { const uint32_t b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); };
         auto above = [&](uint32_t m) {
           float a = 0.f;
-          for (int w = tid; w < V1; w += NT) if (key(x[w]) > m) a += by_count ? 1.f : wgt[w];
-          return block_sum(a, s_val);
+          for (int w = tid; w < V1; w += NT) if (fkey(x[w]) > m) a += by_count ? 1.f : wgt[w];
+          return block_sum<NT>(a, s_val);
         };
-        uint32_t lo = 0x007fffffu, hi = key(bv);             // key(-inf) .. key(row maximum): F(hi) = 0 < limit
+        uint32_t lo = 0x007fffffu, hi = fkey(bv);            // fkey(-inf) .. fkey(row maximum): F(hi) = 0 < limit
         while (lo < hi) {                                    // (uniform: every thread holds the same reduction results)
           const uint32_t mid = lo + ((hi - lo) >> 1);
           if (above(mid) < limit) hi = mid; else lo = mid + 1;
         }
         const float front = above(hi);
         float eq = 0.f;
-        for (int w = tid; w < V1; w += NT) eq += key(x[w]) == hi ? 1.f : 0.f;
-        const bool ties = block_sum(eq, s_val) > 1.f;        // several entries share the boundary value: they enter in index order
+        for (int w = tid; w < V1; w += NT) eq += fkey(x[w]) == hi ? 1.f : 0.f;
+        const bool ties = block_sum<NT>(eq, s_val) > 1.f;    // several entries share the boundary value: they enter in index order
         for (int w = tid; w < V1; w += NT) {
-          const uint32_t kx = key(x[w]);
+          const uint32_t kx = fkey(x[w]);
           bool keep = kx >= hi;
           if (ties && kx == hi) {
             int ahead = 0;
-            for (int j = 0; j < w; ++j) ahead += key(x[j]) == hi ? 1 : 0;
+            for (int j = 0; j < w; ++j) ahead += fkey(x[j]) == hi ? 1 : 0;
             keep = front + (float)ahead * (by_count ? 1.f : wgt[w]) < limit;
           }
           kept[w] = keep ? wgt[w] : 0.f;
         }
       }
-      __syncthreads();
-      // running sum in vocabulary order: a thread owns a contiguous piece, a wave scans its 64 pieces, wave totals meet in LDS
-      const int C = (V1 + NT - 1) / NT, c0 = tid * C, c1 = min(V1, c0 + C);
-      float own = 0.f;
-      for (int j = c0; j < c1; ++j) own += kept[j];
-      float inc = own;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(inc, o, 64); if (lane >= o) inc += up; }
-      if (lane == 63) s_scan[wave] = inc;
-      __syncthreads();
-      float base = 0.f, all = 0.f;
-#pragma unroll
-      for (int w = 0; w < NT / 64; ++w) { if (w < wave) base += s_scan[w]; all += s_scan[w]; }
-      const float target = u * all;
-      float run = base + inc - own;
-      float cv = -INFINITY; int ci = 0x7fffffff;              // the first column whose running sum exceeds the target: arg-max of (0, lowest index)
-      int last = -1;                                          // the highest kept column (target >= the rounded total: u next to 1)
-      for (int j = c0; j < c1; ++j) {
-        const float k = kept[j];
-        run += k;
-        if (k > 0.f) last = j;
-        if (ci == 0x7fffffff && run > target) { cv = 0.f; ci = j; }
-      }
-      block_argmax(cv, ci, s_val, s_idx);
-      if (ci == 0x7fffffff) {
-        float lv = last < 0 ? -INFINITY : 0.f; int li = last < 0 ? 0x7fffffff : -last;      // highest index = lowest negated index among equal keys
-        block_argmax(lv, li, s_val, s_idx);
-        ci = li == 0x7fffffff ? it : -li;
-      }
-      it = ci;
+      it = draw_inverse_cdf<NT>(V1, u, it, [&](int j) { return kept[j]; }, s_scan, s_val, s_idx);
     }
     // ---- 5. finished rows emit [PAD]; a row finishes when it emits [EOS]
     if (tid == 0) {
@@ -193,13 +129,7 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const SampleP p) {
       p.unfinished[r] = unf ? 1 : 0;
     }
   }
-  if (p.pos_out) {
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (atomicAdd(p.ticket, 1) == (int)gridDim.x - 1) { *p.ticket = 0; p.pos_out[0] = t + 1; }
-    }
-  }
+  if (p.pos_out) advance_position(p.pos_out, p.ticket, t);
 }
 
 }  // namespace

@@ -412,6 +412,66 @@ def test_beam_step_kernel_against_the_torch_formulation(beam, B, f32_mem, last):
         assert bool(end[0].any()) or last or B == 1                  # the planted [EOS] was selected (the finished-beam branch ran)
 
 
+@pytest.mark.parametrize('V1', [23, 1537])
+def test_beam_step_without_a_comparable_candidate_keeps_every_hypothesis(V1):
+    """C ABI: evk_beam_step on a study whose log-probabilities are ALL NaN, next to a finite one.  No candidate of such a study compares, so
+    slot r keeps its own hypothesis and emits token 0 at a running sum of -inf: sequences, cache row table and memory rows stay where they
+    are (only column pos takes the 0 and column pos + 1 of the row table is seeded), nothing finishes.  Both kernels behind the entry point:
+    V1 = 23 takes the register kernel, V1 = 1537 is the smallest vocabulary that takes the batched-walk kernel in an ordinary process (it
+    used to form a source row from its sentinel index there).  The finite study is held to the restatement of the test above."""
+    from evoke_amd import hip as H
+    B, beam, max_len, pos0, mem_row, eos = 2, 3, 8, 3, 8, V1 - 2
+    ld = (V1 + 7) // 8 * 8
+    g = torch.Generator().manual_seed(77)
+    logp = torch.log_softmax(torch.randn(B * beam, V1, generator=g) * 2.0, -1)
+    logp[1, eos] = 0.5                                               # an [EOS] that wins in study 0
+    logp[beam:] = float('nan')
+    lp_pad = torch.full((B * beam, ld), -7.0)
+    lp_pad[:, :V1] = logp
+    beam_sum = torch.randn(B, beam, generator=g)
+    beam_seq = torch.randint(5, V1 - 3, (B, beam, max_len), generator=g)
+    beam_seq[:, :, pos0:] = 0
+    best_p = torch.full((B,), -float('inf'))
+    best_seq = torch.randint(5, V1 - 3, (B, max_len), generator=g)
+    mem = torch.randn(B * beam, mem_row, generator=g).to(BF)
+    anc = torch.randint(0, B * beam, (B * beam, max_len), generator=g, dtype=torch.int32)
+    d = lambda t: t.clone().cuda()                                   # noqa: E731
+    lp_d, bs_d, sq_d, bp_d, bq_d, mem_d, anc_d = d(lp_pad), d(beam_sum), d(beam_seq), d(best_p), d(best_seq), d(mem), d(anc)
+    words = torch.full((B * beam,), -1, dtype=torch.long, device='cuda')
+    pos = torch.tensor([pos0], dtype=torch.long, device='cuda')
+    ticket = torch.zeros(1, dtype=torch.int32, device='cuda')
+    H.check(H.lib.evk_beam_step(H.ptr(lp_d), ld, V1, beam, B, max_len, H.ptr(pos), eos, 0, H.ptr(bs_d), H.ptr(sq_d), H.ptr(bp_d), H.ptr(bq_d),
+                                H.ptr(words), H.ptr(mem_d), mem_row, H.ptr(anc_d), max_len, H.ptr(pos), H.ptr(ticket), None, H.stream()), 'beam_step')
+    torch.cuda.synchronize()
+    got_seq, got_sum, got_mem, got_anc, got_words = sq_d.cpu(), bs_d.cpu(), mem_d.cpu(), anc_d.cpu().view(B, beam, max_len), words.cpu().view(B, beam)
+    seeded = torch.arange(B * beam, dtype=torch.int32).view(B, beam)
+    # ---- study 1: nothing compares
+    want_seq = beam_seq[1].clone()
+    want_seq[:, pos0] = 0
+    want_anc = anc.view(B, beam, max_len)[1].clone()
+    want_anc[:, pos0 + 1] = seeded[1]
+    assert torch.equal(got_seq[1], want_seq) and torch.equal(got_words[1], torch.zeros(beam, dtype=torch.long))
+    assert bool((got_sum[1] == -float('inf')).all())
+    assert float(bp_d[1]) == -float('inf') and torch.equal(bq_d.cpu()[1], best_seq[1])
+    assert torch.equal(got_mem[beam:], mem[beam:]) and torch.equal(got_anc[1], want_anc)
+    # ---- study 0: the reference's bookkeeping, restated on the CPU
+    cand = (beam_sum[0].unsqueeze(-1) + logp[:beam]).reshape(-1)
+    order = torch.sort(cand, descending=True, stable=True).indices[:beam]
+    ys, src, word = cand[order], order // V1, order % V1
+    want_seq = beam_seq[0][src].clone()
+    want_seq[:, pos0] = word
+    want_anc = anc.view(B, beam, max_len)[0][src].clone()
+    want_anc[:, pos0 + 1] = seeded[0]
+    end = word == eos
+    assert bool(end.any())                                           # the planted [EOS] was selected
+    assert torch.equal(got_seq[0], want_seq) and torch.equal(got_words[0], word)
+    assert torch.allclose(got_sum[0], ys - 1000.0 * end.float(), atol=1e-5, rtol=0)
+    assert torch.equal(got_mem[:beam], mem[:beam][src]) and torch.equal(got_anc[0], want_anc)
+    fin = int(torch.nonzero(end)[0])                                 # (descending: the first finished beam is the best one)
+    assert abs(float(bp_d[0]) - float(ys[fin])) <= 1e-5 and torch.equal(bq_d.cpu()[0], want_seq[fin])
+    assert int(pos.item()) == pos0 + 1 and int(ticket.item()) == 0
+
+
 def test_dropout_statistics_and_backward():
     from evoke_amd import ops
     x = torch.ones(1 << 16, dtype=BF).cuda().requires_grad_(True)
